@@ -13,11 +13,18 @@ RCCL all-reduce (sum nodes/leaves, max depth) and checked bit-exact against
 the published tree statistics every step. Scaling is STRONG (the tree is
 fixed as N grows); T3L is span-bound (17,844 dependent SHA-1 levels).
 
-At N=1 the same JSON line also carries the other BASELINE configs measured
-in the same process (T1 nodes/s, forasync triad HBM GB/s with its roofline,
-fib(30) tasks/s, Smith-Waterman 64K cells/s) and the host-CPU baseline: the
-repo's C restatement of HClib's work-stealing runtime (oracle/, "port") on
-T3L with the box's CPU share.
+A plain run does that and no more: set up, warm up, time the K steps, print
+the line (`value`, `ms_per_step`, the per-rank kernel times). `--dump-outputs
+DIR` also writes the counts the last timed step returned as DIR/*.npy.
+
+    python bench.py --full [--gpus N ...]
+
+With `--full` the same JSON line also carries, at N=1, the other BASELINE
+configs measured in the same process (T1 nodes/s, forasync triad HBM GB/s
+with its roofline, fib(30) tasks/s, Smith-Waterman 64K cells/s) and the
+host-CPU baseline: the repo's C restatement of HClib's work-stealing runtime
+(oracle/, "port") on T3L with the box's CPU share; at N>1, T(1) with the
+strong-scaling efficiency and the sharded legs (`--no-extras` skips those).
 """
 from __future__ import annotations
 
@@ -546,6 +553,21 @@ def sharded_sw(H, rank, world, be, steps=2):
     return out
 
 
+def dump_outputs(dirname, counts, nodes_per_rank):
+    """--dump-outputs: what the last timed step returned to its caller, one
+    .npy per array (float64: every count is far below 2^53, so exact). The
+    search has no input data (the tree grows from T3L's published parameters),
+    so two builds given the same arguments must write the same arrays.
+    Scheduler statistics and timings, which differ run to run, are left out."""
+    import numpy as np
+
+    os.makedirs(dirname, exist_ok=True)
+    # whole-job (nodes, leaves, max_depth); at N = 1 exactly H.uts(T3L)'s counts
+    np.save(os.path.join(dirname, "counts.npy"), np.asarray(counts, dtype=np.float64))
+    # the nodes each rank's search returned (one entry at N = 1)
+    np.save(os.path.join(dirname, "nodes_per_rank.npy"), np.asarray(nodes_per_rank, dtype=np.float64))
+
+
 def _free_port() -> int:
     import socket
 
@@ -646,12 +668,23 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--split", type=int, default=1,
                     help="depth at which T3L's nodes are hashed to ranks (the levels above are replicated)")
-    ap.add_argument("--no-extras", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything else the line can carry: the other "
+                         "BASELINE configs, the rooflines, the atomics figures, the host-CPU baselines and, "
+                         "at N > 1, T(1) and the sharded legs (a plain run reports the headline only)")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the extra legs (at N > 1 only T(1) is still measured)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float64)")
     ap.add_argument("--backend", default="nccl",
                     help="collective backend (nccl = RCCL; gloo only for rehearsals)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal on a 1-GPU box: every rank uses device 0 (with --backend gloo)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    # the headline needs the timed steps only; every other leg is --full's
+    extras = args.full and not args.no_extras
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one (before any torch / HIP call)
         sys.exit(self_launch(sys.argv[1:], args.gpus))
@@ -691,8 +724,10 @@ def main():
     value = T3L_GOLD[0] * args.steps / elapsed
     per_rank_ms = dist.gather_floats(sum(kernel_ms) / len(kernel_ms), world, be)
     per_rank_nodes = dist.gather_floats(float(last["nodes"]), world, be)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tot, per_rank_nodes)
     t3l_one = None
-    if world > 1:
+    if world > 1 and args.full:
         # T(1): the whole tree on each GPU alone, outside the timed region
         dist.barrier(world, be)
         t1 = time.perf_counter()
@@ -704,11 +739,11 @@ def main():
     # skipped on every rank, and the line still prints within the bound
     legs = dist.LegGuard(world, float(os.environ.get("HCLIB_BENCH_LEG_TIMEOUT_S", "120")),
                          device=(0 if args.share_device else local) if be == "nccl" or args.share_device else None) \
-        if world > 1 else None
+        if world > 1 and args.full else None
     guarded = (lambda name, fn: legs.run(name, fn)) if legs else (lambda name, fn: fn())
-    wide = None if args.no_extras else guarded("wide_tree", lambda: wide_tree(H, rank, world, be))
+    wide = guarded("wide_tree", lambda: wide_tree(H, rank, world, be)) if extras else None
     shard_tri = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         # the 2^28 triad block-sharded over the ranks (no
         # exchange); whole-job GB/s over the slowest rank's launch time
         def sharded_triad():
@@ -721,10 +756,10 @@ def main():
                     "bit_exact": ok}
         shard_tri = guarded("forasync_sharded", sharded_triad)
     shard_sw = None
-    if world > 1 and not args.no_extras:
+    if world > 1 and extras:
         shard_sw = guarded("sw_sharded", lambda: sharded_sw(H, rank, world, be))
     skewed = None
-    if world > 1 and not args.no_extras and os.environ.get("HCLIB_BENCH_SHARE_WORK", "1") != "0":
+    if world > 1 and extras and os.environ.get("HCLIB_BENCH_SHARE_WORK", "1") != "0":
         skewed = guarded("uts_work_sharing", lambda: skewed_sharing(H, rank, world, be))
     # a stall anywhere (this rank's guard, or another rank's flag in the
     # store) ends every rank the same way: no orderly shutdown (a leg's thread
@@ -777,7 +812,7 @@ def main():
         out["sw_sharded"] = shard_sw
     if skewed:
         out["uts_work_sharing"] = skewed
-    if world == 1 and not args.no_extras:
+    if world == 1 and extras:
         tri = measure_triad(H)
         traffic = load_pmc_traffic()
         out["roofline"] = {

@@ -11,7 +11,7 @@ rc=$?
 tail -3 $OUT/$TAG.log
 [ $rc -ne 0 ] && exit $rc
 if [ "$BENCH" = 1 ]; then
-  timeout -k 10 400 python -u bench.py > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit $?
+  timeout -k 10 400 python -u bench.py --full > $OUT/bench_$TAG.json 2> $OUT/bench_$TAG.err || exit $?
   python3 -c "
 import json; d=json.load(open('$OUT/bench_$TAG.json'))
 c=d['configs']

@@ -10,10 +10,10 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 timeout -k 10 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread > $OUT/full_tests.log 2>&1 &&
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print(\"smoke ok\")" > $OUT/smoke.log 2>&1 &&
-timeout -k 10 400 python -u bench.py > $OUT/bench.json 2> $OUT/bench.err &&
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.json 2> $OUT/bench.err &&
 if [ "${FULL:-1}" = 0 ]; then echo ok; exit 0; fi &&
 rm -rf $OUT/prof &&
-timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 -u bench.py > $OUT/bench_prof.json 2> $OUT/bench_prof.err &&
+timeout -k 10 500 rocprofv3 --kernel-trace --stats -d $OUT/prof -o run -- python3 -u bench.py --full > $OUT/bench_prof.json 2> $OUT/bench_prof.err &&
 rm -rf gpurun_out/pmc gpurun_out/pmcu_t1xl gpurun_out/pmcu_t3l &&
 bash scripts/pmc_triad.sh > $OUT/pmc_triad.log 2>&1 &&
 bash scripts/pmc_uts.sh T1XL 0 gpurun_out/pmcu_t1xl > $OUT/pmc_t1xl.log 2>&1 &&

@@ -671,3 +671,35 @@ def test_bench_self_launch_two_ranks_one_gpu():
     assert ln["collectives"]["world_size"] == 2 and ln["n_gpus"] == 2
     assert ln["config"]["bit_exact"] and sum(ln["nodes_per_rank"]) == 111345631
     assert "self-launch" in ln["launcher"]
+
+
+# ------------------------------------------------- bench.py, the plain run
+def test_bench_plain_run_is_lean_and_dumps_outputs(tmp_path):
+    """`python bench.py --gpus 1 --steps 2 --warmup 0` measures the headline
+    only (none of --full's legs in the line), `--steps` is the number of timed
+    steps, `ms_per_step` agrees with `value`, and --dump-outputs writes what
+    the last step returned: T3L's published counts
+    (test/uts/sample_trees.sh:42-43), exact in float64."""
+    import json
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path / "out")],
+                       cwd=root, env=env, capture_output=True, text=True, timeout=115)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [json.loads(x) for x in r.stdout.splitlines() if x.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    ln = lines[0]
+    assert ln["steps"] == 2 and ln["warmup"] == 0 and ln["n_gpus"] == 1
+    assert ln["unit"] == "nodes/s" and ln["higher_is_better"] is True and ln["dtype"] == "u32"
+    assert ln["ms_per_step"] > 0
+    assert abs(ln["value"] * ln["ms_per_step"] * 1e-3 - 111345631) < 1.0
+    assert len(ln["kernel_ms_per_rank"]) == 1 and ln["kernel_ms_per_rank"][0] <= ln["ms_per_step"]
+    for key in ("roofline", "roofline_uts", "configs", "atomics", "cpu_baseline", "cpu_configs", "wide_tree"):
+        assert key not in ln, key
+    counts = np.load(tmp_path / "out" / "counts.npy")
+    assert counts.dtype == np.float64 and counts.tolist() == [111345631.0, 89076904.0, 17844.0]
+    assert np.load(tmp_path / "out" / "nodes_per_rank.npy").tolist() == [111345631.0]
