@@ -82,6 +82,13 @@ class SwResult(C.Structure):
                 ("cells_per_s", C.c_double), ("tile_us", C.c_double), ("release_us", C.c_double)]
 
 
+class AtomicViewStruct(C.Structure):
+    """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
+
+    _fields_ = [("slots", C.c_void_p), ("nslots", C.c_uint32), ("stride", C.c_uint32),
+                ("dtype", C.c_int), ("op", C.c_int)]
+
+
 # every symbol include/hclib_hip.h and include/hclib.h declare (checked by tests)
 EXPORTS_HIP = [
     "hclib_hip_init", "hclib_hip_finalize", "hclib_hip_last_error", "hclib_hip_num_cus",
@@ -91,6 +98,10 @@ EXPORTS_HIP = [
     "hclib_hip_fib", "hclib_hip_sw", "hclib_hip_last_sched_counters", "hclib_hip_last_narrow_counters",
     "hclib_hip_last_phase_counters",
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
+    "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
+    "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
+    "hclib_hip_forasync_reduce",
+    "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
 _lib = None
@@ -144,6 +155,14 @@ def lib():
         L.hclib_hip_ipc_import.argtypes = [C.c_void_p, C.POINTER(C.c_void_p)]
         L.hclib_hip_ipc_close.argtypes = [C.c_void_p]
         L.hclib_hip_last_timeline.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint32)]
+        L.hclib_hip_atomic_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.POINTER(C.c_void_p)]
+        L.hclib_hip_atomic_destroy.argtypes = [C.c_void_p]
+        L.hclib_hip_atomic_view.argtypes = [C.c_void_p, C.POINTER(AtomicViewStruct)]
+        L.hclib_hip_atomic_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hclib_hip_atomic_gather_async.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.hclib_hip_atomic_reset.argtypes = [C.c_void_p, C.c_void_p]
+        L.hclib_hip_forasync_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LoopDomain),
+                                                C.c_int, C.c_void_p]
         _lib = L
     return _lib
 
@@ -184,6 +203,78 @@ def forasync(body: int, args: C.Structure, domains, mode: int, stream: Optional[
 def triad_f32(a_ptr: int, b_ptr: int, c_ptr: int, s: float, n: int, stream: Optional[int] = None):
     _check(lib().hclib_hip_forasync_triad_f32(a_ptr, b_ptr, c_ptr, s, n, stream),
            "hclib_hip_forasync_triad_f32")
+
+
+# ------------------------------------------------------- privatised atomics
+ATOMIC_DTYPES = {"int32": (0, C.c_int32), "uint32": (1, C.c_uint32), "int64": (2, C.c_int64),
+                 "uint64": (3, C.c_uint64), "float32": (4, C.c_float), "float64": (5, C.c_double)}
+ATOMIC_OPS = {"sum": 0, "max": 1, "or": 2}
+
+
+class Atomic:
+    """A privatised atomic in device memory (hclib_hip_atomic_*, the device
+    form of inc/hclib_atomic.h): one slot per wave, folded by gather().
+    dtype is a key of ATOMIC_DTYPES (or anything whose str() ends in one, such
+    as a numpy or torch dtype), op one of "sum", "max", "or" (logical or:
+    0 or 1). Updates accumulate over launches until reset()."""
+
+    def __init__(self, dtype, op: str, default=0):
+        name = str(getattr(dtype, "__name__", dtype)).rsplit(".", 1)[-1]
+        if name not in ATOMIC_DTYPES:
+            raise ValueError(f"Atomic: dtype {dtype!r} is not one of {sorted(ATOMIC_DTYPES)}")
+        if op not in ATOMIC_OPS:
+            raise ValueError(f"Atomic: op {op!r} is not one of {sorted(ATOMIC_OPS)}")
+        self.dtype, self.op = name, op
+        code, self._ctype = ATOMIC_DTYPES[name]
+        h = C.c_void_p()
+        _check(lib().hclib_hip_atomic_create(code, ATOMIC_OPS[op], C.byref(self._ctype(default)), C.byref(h)),
+               "hclib_hip_atomic_create")
+        self._h = h
+
+    def _handle(self):
+        if self._h is None:
+            raise HclibError("Atomic: used after close()")
+        return self._h
+
+    def view(self) -> AtomicViewStruct:
+        v = AtomicViewStruct()
+        _check(lib().hclib_hip_atomic_view(self._handle(), C.byref(v)), "hclib_hip_atomic_view")
+        return v
+
+    def gather(self, stream: Optional[int] = None):
+        """Fold the slots on `stream` and wait; the value as a Python number."""
+        out = self._ctype()
+        _check(lib().hclib_hip_atomic_gather(self._handle(), stream, C.byref(out)), "hclib_hip_atomic_gather")
+        return out.value
+
+    def gather_async(self, device_out: int, stream: Optional[int] = None) -> None:
+        _check(lib().hclib_hip_atomic_gather_async(self._handle(), stream, device_out),
+               "hclib_hip_atomic_gather_async")
+
+    def reset(self, stream: Optional[int] = None) -> None:
+        _check(lib().hclib_hip_atomic_reset(self._handle(), stream), "hclib_hip_atomic_reset")
+
+    def close(self) -> None:
+        h, self._h = self._h, None
+        if h is not None:
+            _check(lib().hclib_hip_atomic_destroy(h), "hclib_hip_atomic_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def forasync_reduce(atomic: Atomic, ptr: int, domains, mode: int, stream: Optional[int] = None):
+    """atomic.update(x[i]) over the forasync iteration set of the 1-D domain
+    (hclib_hip_forasync_reduce); ptr is the device address of x, whose
+    elements have the atomic's dtype. Asynchronous on `stream`; returns the
+    domains after the tile == -1 write-back, like forasync()."""
+    dims = (LoopDomain * len(domains))(*[LoopDomain(*d) for d in domains])
+    _check(lib().hclib_hip_forasync_reduce(atomic._handle(), ptr, len(domains), dims, mode, stream),
+           "hclib_hip_forasync_reduce")
+    return [(d.low, d.high, d.stride, d.tile) for d in dims]
 
 
 # ----------------------------------------------------------------------- UTS

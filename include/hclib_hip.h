@@ -28,6 +28,9 @@
  *                                    :119-239
  *   hclib_hip_dag_*                  the same dependency-counter release for any
  *                                    async_await DAG built through hclib.h
+ *   hclib_hip_atomic_*,              the per-thread copies and the gather of
+ *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
+ *                                    src/hclib_atomic.c:34-54, one slot per wave
  *
  * Conventions (mirroring the reference's error behaviour):
  * plain pointers and sizes only; functions return 0 on success and a
@@ -230,6 +233,68 @@ typedef struct {
 int hclib_hip_forasync_plan(int dim, hclib_hip_loop_domain_t *domain, int mode, void *stream,
                             hclib_hip_sweep_plan_t *plan);
 int hclib_hip_forasync_plan_release(hclib_hip_sweep_plan_t *plan, void *stream);
+
+/* ---------------------------------------------------- privatised atomics */
+/* The device form of inc/hclib_atomic.h (hclib_atomic_t and the C++
+ * atomic_sum_t / atomic_max_t / atomic_or_t, inc/hclib_atomic.h:37-42,
+ * 141-186): one padded slot per worker, updated without contention and folded
+ * on request. A device worker is a wave; device code updates through
+ * hx::AtomicView (include/hclib_hip/hx_atomic.h), the host creates, gathers
+ * and resets through the calls below.
+ *
+ * create   allocates nslots slots of HCLIB_HIP_ATOMIC_STRIDE bytes (nslots: a
+ *          power of two >= the worker count of every launch this library
+ *          makes) plus one result word, and resets them. `default_value`
+ *          points to one value of `dtype`. MAX and OR start every slot at the
+ *          default; SUM starts every slot at zero and adds the default once
+ *          at the gather (nslots copies of a non-zero default must not be
+ *          summed), so an atomic always reads its default after a reset. OR
+ *          is the reference's logical or: the result is 0 or 1.
+ * view     fills the struct device code is handed (by value).
+ * gather   one workgroup folds the slots in a fixed tree order into the
+ *          result word, in `stream` order; the call then copies the word to
+ *          host_out (one value of dtype) and waits. Gather does not reset:
+ *          updates of successive launches accumulate, as the reference's
+ *          gather leaves the per-thread copies alone (src/hclib_atomic.c:40-54).
+ * gather_async  the same fold into device memory `device_out`, no wait.
+ * reset    every slot back to its start value, in `stream` order.
+ * destroy  waits for the device, then frees. */
+#define HCLIB_HIP_ATOMIC_I32 0
+#define HCLIB_HIP_ATOMIC_U32 1
+#define HCLIB_HIP_ATOMIC_I64 2
+#define HCLIB_HIP_ATOMIC_U64 3
+#define HCLIB_HIP_ATOMIC_F32 4
+#define HCLIB_HIP_ATOMIC_F64 5
+#define HCLIB_HIP_ATOMIC_SUM 0
+#define HCLIB_HIP_ATOMIC_MAX 1
+#define HCLIB_HIP_ATOMIC_OR 2
+#define HCLIB_HIP_ATOMIC_STRIDE 128 /* bytes between slots: one L2 line each */
+
+typedef struct hclib_hip_atomic hclib_hip_atomic_t;
+typedef struct {
+    void *slots;     /* device pointer to slot 0 */
+    uint32_t nslots; /* power of two */
+    uint32_t stride; /* bytes between slots */
+    int dtype, op;
+} hclib_hip_atomic_view_t;
+
+int hclib_hip_atomic_create(int dtype, int op, const void *default_value, hclib_hip_atomic_t **out);
+int hclib_hip_atomic_destroy(hclib_hip_atomic_t *atomic);
+int hclib_hip_atomic_view(const hclib_hip_atomic_t *atomic, hclib_hip_atomic_view_t *view);
+int hclib_hip_atomic_gather(hclib_hip_atomic_t *atomic, void *stream, void *host_out);
+int hclib_hip_atomic_gather_async(hclib_hip_atomic_t *atomic, void *stream, void *device_out);
+int hclib_hip_atomic_reset(hclib_hip_atomic_t *atomic, void *stream);
+
+/* A reducing forasync with the built-in body `update(x[i])`: x is a device
+ * array of the atomic's dtype, indexed by the iterations of the 1-D `domain`
+ * (dim must be 1) exactly as hclib_hip_forasync enumerates them for `mode`
+ * (tile == -1 resolved and written back likewise). Every thread keeps its
+ * partial value in a register, every wave updates its slot once. One
+ * unit-stride run is read with 16-byte loads (alignment prologue and tail
+ * included); any other set goes through the run tables. Asynchronous on
+ * `stream`; read the value with hclib_hip_atomic_gather. */
+int hclib_hip_forasync_reduce(hclib_hip_atomic_t *atomic, const void *x, int dim, hclib_hip_loop_domain_t *domain,
+                              int mode, void *stream);
 
 /* ----------------------------------------------------------------- UTS */
 /* Tree parameters: the UTS CLI flags of test/uts/uts.c:380-420 (same field

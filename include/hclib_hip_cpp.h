@@ -13,6 +13,16 @@
  *       (include/hclib_forasync_sets.h). Blocking, like the reference's
  *       finish-wrapped forasync; the _nb forms return after enqueueing.
  *
+ *   hclib::hip::atomic_sum_t<T> / atomic_max_t<T> / atomic_or_t<T>
+ *   hclib::hip::forasync{1,2,3}D_gather(loop, atomic, body, mode)
+ *       hclib::atomic_sum_t / atomic_max_t / atomic_or_t (inc/hclib_atomic.h:
+ *       141-186) for device code: host objects whose view() is captured by a
+ *       __device__ lambda or kept in a Kind::Ctx and updated with +=, update
+ *       and |= (include/hclib_hip/hx_atomic.h: one slot per wave); get()
+ *       folds the slots. forasync*_gather is the reducing sweep: body returns
+ *       a value per iteration, partials stay in registers and every wave
+ *       updates its slot once.
+ *
  *   hclib::hip::dag + run_dag<Kind>(ctx, graph, &stats)
  *       hclib::promise_t / async_await for device tasks: the host declares
  *       promises and tasks (each with a payload and the futures it awaits,
@@ -49,6 +59,7 @@
 
 #include "hclib_cpp.h"
 #include "hclib_hip.h"
+#include "hclib_hip/hx_atomic.h"
 #include "hclib_hip/hx_dag.h"
 #include "hclib_hip/hx_dyn.h"
 #include "hclib_hip/hx_finish.h"
@@ -165,7 +176,70 @@ __global__ __launch_bounds__(256) void k_forasync_runs(RunTable t0, RunTable t1,
     }
 }
 
+// The reducing forms (forasync*_gather): G = detail::GatherBody, whose body
+// returns a value per iteration; the thread folds them in a register and the
+// wave updates the atomic once, after its last iteration (all lanes active)
+template <typename G>
+__global__ __launch_bounds__(256) void k_forasync_run_gather(hclib_sets::Run r, G g) {
+    using T = typename G::value_type;
+    using Op = typename G::op_type;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    T acc = Op::template identity<T>();
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < r.count; t += step)
+        acc = Op::template combine<T>(acc, (T)g.body(r.first + (int)t * r.stride));
+    g.view.update(acc);
+}
+
+template <int ND, typename G>
+__global__ __launch_bounds__(256) void k_forasync_runs_gather(RunTable t0, RunTable t1, RunTable t2, int64_t n1,
+                                                              int64_t n2, int64_t total, G g) {
+    using T = typename G::value_type;
+    using Op = typename G::op_type;
+    const int64_t step = (int64_t)gridDim.x * blockDim.x;
+    T acc = Op::template identity<T>();
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += step) {
+        if constexpr (ND == 1) {
+            acc = Op::template combine<T>(acc, (T)g.body(run_idx(t0, t)));
+        } else if constexpr (ND == 2) {
+            acc = Op::template combine<T>(acc, (T)g.body(run_idx(t0, t / n1), run_idx(t1, t % n1)));
+        } else {
+            const int64_t r = t / n2;
+            acc = Op::template combine<T>(acc, (T)g.body(run_idx(t0, r / n1), run_idx(t1, r % n1), run_idx(t2, t % n2)));
+        }
+    }
+    g.view.update(acc);
+}
+
 namespace detail {
+
+// which kernels launch_runs starts: the plain sweep, or the reducing one
+struct SweepKernels {
+    template <typename F>
+    static auto run() {
+        return &k_forasync_run<F>;
+    }
+    template <int ND, typename F>
+    static auto runs() {
+        return &k_forasync_runs<ND, F>;
+    }
+};
+struct GatherKernels {
+    template <typename G>
+    static auto run() {
+        return &k_forasync_run_gather<G>;
+    }
+    template <int ND, typename G>
+    static auto runs() {
+        return &k_forasync_runs_gather<ND, G>;
+    }
+};
+template <typename T, typename Op, typename Body>
+struct GatherBody {
+    using value_type = T;
+    using op_type = Op;
+    hx::AtomicView<T, Op> view;
+    Body body;
+};
 
 inline int num_workers() {
     const int n = hclib_hip_num_workers();
@@ -185,7 +259,7 @@ inline int grid_for(int64_t total) {
 }
 
 // Upload the run tables of `nd` dimensions, launch, and (blocking) wait.
-template <int ND, typename F>
+template <int ND, typename F, typename K = SweepKernels>
 int launch_runs(std::vector<hclib_sets::Run> *r, F f, hipStream_t s, bool blocking) {
     int64_t n[3] = {1, 1, 1}, total = 1;
     for (int d = 0; d < ND; ++d) {
@@ -196,7 +270,7 @@ int launch_runs(std::vector<hclib_sets::Run> *r, F f, hipStream_t s, bool blocki
     bool single = false;
     if constexpr (ND == 1) {
         if (r[0].size() == 1) {
-            hipLaunchKernelGGL(k_forasync_run<F>, dim3(grid_for(total)), dim3(256), 0, s, r[0][0], f);
+            hipLaunchKernelGGL(K::template run<F>(), dim3(grid_for(total)), dim3(256), 0, s, r[0][0], f);
             single = true;
         }
     }
@@ -220,7 +294,7 @@ int launch_runs(std::vector<hclib_sets::Run> *r, F f, hipStream_t s, bool blocki
             t[d].nruns = (int)r[d].size();
         }
         if (hipMemcpyAsync(dbuf, h.data(), bytes, hipMemcpyHostToDevice, s) != hipSuccess) return HCLIB_HIP_EHIP;
-        hipLaunchKernelGGL((k_forasync_runs<ND, F>), dim3(grid_for(total)), dim3(256), 0, s, t[0], t[1], t[2],
+        hipLaunchKernelGGL((K::template runs<ND, F>()), dim3(grid_for(total)), dim3(256), 0, s, t[0], t[1], t[2],
                            ND > 1 ? n[1] : 1, ND > 2 ? n[2] : 1, total, f);
         if (blocking) {
             if (hipStreamSynchronize(s) != hipSuccess) return HCLIB_HIP_EHIP;
@@ -234,7 +308,7 @@ int launch_runs(std::vector<hclib_sets::Run> *r, F f, hipStream_t s, bool blocki
     return HCLIB_HIP_OK;
 }
 
-template <int ND, typename F>
+template <int ND, typename F, typename K = SweepKernels>
 int forasync(hclib_loop_domain_t *loop, F f, int mode, hipStream_t s, bool blocking) {
     if (hclib_hip_init(0) != HCLIB_HIP_OK) return HCLIB_HIP_ENODEV;
     std::vector<hclib_sets::Run> r[3];
@@ -242,7 +316,15 @@ int forasync(hclib_loop_domain_t *loop, F f, int mode, hipStream_t s, bool block
         if (loop[d].stride < 1) return HCLIB_HIP_EINVAL;
         r[d] = dim_runs(&loop[d], ND, mode);
     }
-    return launch_runs<ND>(r, f, s, blocking);
+    return launch_runs<ND, F, K>(r, f, s, blocking);
+}
+
+// the same sweep with a body that returns a value, reduced into `view`
+// (grid_for keeps the grid at 32 waves per CU, within the atomic's slots)
+template <int ND, typename T, typename Op, typename Body>
+int forasync_gather(hclib_loop_domain_t *loop, const hx::AtomicView<T, Op> &view, Body body, int mode, hipStream_t s) {
+    if (!view.slots) return HCLIB_HIP_EINVAL;
+    return forasync<ND, GatherBody<T, Op, Body>, GatherKernels>(loop, GatherBody<T, Op, Body>{view, body}, mode, s, true);
 }
 
 }  // namespace detail
@@ -270,6 +352,78 @@ int forasync3D(hclib::loop_domain_3d *loop, F f, int mode = FORASYNC_MODE_RECURS
 template <typename F>
 int forasync3D_nb(hclib::loop_domain_3d *loop, F f, int mode = FORASYNC_MODE_RECURSIVE, hipStream_t s = nullptr) {
     return detail::forasync<3>(loop->get_internal(), f, mode, s, false);
+}
+
+// ------------------------------------------------------ privatised atomics
+// hclib::atomic_sum_t / atomic_max_t / atomic_or_t (inc/hclib_atomic.h:141-186)
+// with the GPU's waves as the workers: the host object owns the slots
+// (hclib_hip_atomic_create, include/hclib_hip.h), view() is what device code
+// updates (a POD, by value), get() folds the slots on `stream` and waits.
+// Updates of successive launches accumulate until reset().
+template <typename T, typename Op>
+class device_atomic {
+  public:
+    explicit device_atomic(T default_value) {
+        if (hclib_hip_atomic_create(hx::AtomicDtype<T>::value, Op::kId, &default_value, &h_) != HCLIB_HIP_OK) h_ = nullptr;
+    }
+    ~device_atomic() {
+        if (h_) (void)hclib_hip_atomic_destroy(h_);
+    }
+    device_atomic(const device_atomic &) = delete;
+    device_atomic &operator=(const device_atomic &) = delete;
+    bool ok() const { return h_ != nullptr; }
+    hclib_hip_atomic_t *handle() const { return h_; }
+    hx::AtomicView<T, Op> view() const {
+        hclib_hip_atomic_view_t v = {};
+        if (h_) (void)hclib_hip_atomic_view(h_, &v);
+        return hx::AtomicView<T, Op>{(char *)v.slots, v.nslots, v.stride};
+    }
+    // the fold of every update so far (T() and an error message when the
+    // atomic is not ok() or the device call fails)
+    T get(hipStream_t stream = nullptr) const {
+        T v = T();
+        if (h_) (void)hclib_hip_atomic_gather(h_, stream, &v);
+        return v;
+    }
+    int reset(hipStream_t stream = nullptr) { return h_ ? hclib_hip_atomic_reset(h_, stream) : HCLIB_HIP_EINVAL; }
+
+  private:
+    hclib_hip_atomic_t *h_ = nullptr;
+};
+template <typename T>
+using atomic_sum_t = device_atomic<T, hx::Sum>;
+template <typename T>
+using atomic_max_t = device_atomic<T, hx::Max>;
+template <typename T>
+using atomic_or_t = device_atomic<T, hx::Or>;
+
+// forasync{1,2,3}D whose body returns a value: `atomic` (a device_atomic or
+// its view) receives the reduction over the reference's iteration set for
+// `mode`. Blocking, like forasync{1,2,3}D; read the value with atomic.get().
+namespace detail {
+template <typename T, typename Op>
+inline hx::AtomicView<T, Op> view_of(const device_atomic<T, Op> &a) {
+    return a.view();
+}
+template <typename T, typename Op>
+inline hx::AtomicView<T, Op> view_of(const hx::AtomicView<T, Op> &v) {
+    return v;
+}
+}  // namespace detail
+template <typename A, typename F>
+int forasync1D_gather(hclib::loop_domain_1d *loop, const A &atomic, F body, int mode = FORASYNC_MODE_RECURSIVE,
+                      hipStream_t s = nullptr) {
+    return detail::forasync_gather<1>(loop->get_internal(), detail::view_of(atomic), body, mode, s);
+}
+template <typename A, typename F>
+int forasync2D_gather(hclib::loop_domain_2d *loop, const A &atomic, F body, int mode = FORASYNC_MODE_RECURSIVE,
+                      hipStream_t s = nullptr) {
+    return detail::forasync_gather<2>(loop->get_internal(), detail::view_of(atomic), body, mode, s);
+}
+template <typename A, typename F>
+int forasync3D_gather(hclib::loop_domain_3d *loop, const A &atomic, F body, int mode = FORASYNC_MODE_RECURSIVE,
+                      hipStream_t s = nullptr) {
+    return detail::forasync_gather<3>(loop->get_internal(), detail::view_of(atomic), body, mode, s);
 }
 
 // ------------------------------------------------- user device task kinds
