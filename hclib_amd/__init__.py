@@ -82,6 +82,14 @@ class SwResult(C.Structure):
                 ("cells_per_s", C.c_double), ("tile_us", C.c_double), ("release_us", C.c_double)]
 
 
+class CholeskyResult(C.Structure):
+    """hclib_hip_cholesky_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("puts", C.c_uint64), ("releases", C.c_uint64),
+                ("potrf", C.c_uint64), ("trsm", C.c_uint64), ("syrk", C.c_uint64), ("gemm", C.c_uint64),
+                ("kernel_ms", C.c_double), ("gflops", C.c_double), ("fail_col", C.c_int)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -100,7 +108,7 @@ EXPORTS_HIP = [
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
-    "hclib_hip_forasync_reduce",
+    "hclib_hip_forasync_reduce", "hclib_hip_cholesky",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -163,6 +171,8 @@ def lib():
         L.hclib_hip_atomic_reset.argtypes = [C.c_void_p, C.c_void_p]
         L.hclib_hip_forasync_reduce.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.POINTER(LoopDomain),
                                                 C.c_int, C.c_void_p]
+        L.hclib_hip_cholesky.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                         C.POINTER(CholeskyResult)]
         _lib = L
     return _lib
 
@@ -448,6 +458,61 @@ def sw_map(text: bytes) -> bytes:
     """clear_whitespaces_do_mapping (smith_waterman.cpp:45-59): keep ACGT -> 1..4."""
     table = bytes.maketrans(b"ACGT", b"\x01\x02\x03\x04")
     return bytes(x for x in text if x in b"ACGT").translate(table)
+
+
+# ------------------------------------------------------------------ Cholesky
+CHOL_MODES = {"exact": 0}  # HCLIB_HIP_CHOL_EXACT
+
+
+class NotSPDError(HclibError):
+    """hclib_hip_cholesky met a pivot <= 0 (the reference's "Not a symmetric
+    positive definite (SPD) matrix"); fail_col is the global column."""
+
+    def __init__(self, msg: str, fail_col: int):
+        super().__init__(msg)
+        self.fail_col = fail_col
+
+
+def cholesky(a, tile: int, mode: str = "exact"):
+    """Tiled Cholesky of test/cholesky on the device promise DAG
+    (hclib_hip_cholesky): a is an n x n float64 array whose lower triangle is
+    read; returns (L, stats) with L lower triangular (+0.0 above the diagonal).
+    mode "exact" (the one mode) is bit-identical to the reference for every
+    tile size."""
+    import numpy as np
+
+    if mode not in CHOL_MODES:
+        raise ValueError(f"cholesky: mode {mode!r} is not one of {sorted(CHOL_MODES)}")
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise ValueError("cholesky: a must be a square matrix")
+    out = np.empty_like(a)
+    r = CholeskyResult(fail_col=-1)
+    rc = lib().hclib_hip_cholesky(a.ctypes.data, a.shape[0], tile, CHOL_MODES[mode], out.ctypes.data, C.byref(r))
+    if rc != HCLIB_HIP_OK and r.fail_col >= 0:
+        msg = lib().hclib_hip_last_error().decode(errors="replace")
+        raise NotSPDError(f"hclib_hip_cholesky failed ({rc}): {msg}", r.fail_col)
+    _check(rc, "hclib_hip_cholesky")
+    return out, {k: getattr(r, k) for k, _ in CholeskyResult._fields_}
+
+
+def cholesky_read(path: str, n: int):
+    """The reference's input reader (cholesky.cpp:57-61): n * n numbers
+    separated by whitespace, row by row."""
+    import numpy as np
+
+    with open(path) as f:
+        vals = f.read().split()
+    if len(vals) < n * n:
+        raise ValueError(f"cholesky_read: {path} holds {len(vals)} values, {n}x{n} needs {n * n}")
+    return np.array(vals[:n * n], dtype=np.float64).reshape(n, n)
+
+
+def cholesky_format(L) -> str:
+    """The reference's cholesky.out writer (cholesky.cpp:129-147): row by row
+    the lower triangle, each value as "%lf " (six decimals), no newlines."""
+    n = L.shape[0]
+    return "".join("%f " % v for i in range(n) for v in L[i, :i + 1].tolist())
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

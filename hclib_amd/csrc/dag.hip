@@ -238,6 +238,10 @@ extern "C" int hclib_hip_dag_end(const char *who, uint64_t *datum_out, uint8_t *
                   (unsigned long long)st[0], g_dag.ntasks);
         return HCLIB_HIP_EDEVICE;
     }
+    if (err == kErrNotSpd) {
+        set_error("%s: Not a symmetric positive definite (SPD) matrix", w);
+        return HCLIB_HIP_EDEVICE;
+    }
     if (err) {
         set_error("%s: device error %u", w, err);
         return HCLIB_HIP_EDEVICE;

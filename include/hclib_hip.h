@@ -28,6 +28,9 @@
  *                                    :119-239
  *   hclib_hip_dag_*                  the same dependency-counter release for any
  *                                    async_await DAG built through hclib.h
+ *   hclib_hip_cholesky               the k-loop and its two finish scopes per step
+ *                                    of test/cholesky/cholesky.cpp:80-124, with the
+ *                                    four tile kernels, as one promise-DAG launch
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -512,6 +515,33 @@ int hclib_hip_sw_band_begin(const int8_t *s1, size_t n1, const int8_t *s2, size_
 int hclib_hip_sw_band_rows(hclib_hip_sw_band_t *band, int i0, int i1, const int *left_in, int *right_out,
                            void *stream);
 int hclib_hip_sw_band_end(hclib_hip_sw_band_t *band, void *stream, int *corner, uint64_t *tiles);
+
+/* ----------------------------------------------------------- Cholesky */
+/* The tiled Cholesky factorisation of test/cholesky (cholesky.cpp:80-124 and
+ * its four tile kernels) as ONE launch of the device promise DAG: one promise
+ * per tile version lkji[j][i][k], one workgroup task per tile kernel, no
+ * barrier between the steps. `a` and `l` are host arrays, row-major n x n
+ * (`l` may be `a`); only the lower triangle of `a` is read, `l` receives the
+ * factor in its lower triangle and +0.0 above it. n % tile == 0 (the
+ * reference's own check), tile <= 128.
+ *   HCLIB_HIP_CHOL_EXACT  (the one mode) every element sees the reference's
+ *       operations in the reference's order (unfused multiply and add,
+ *       ascending k, IEEE divide and square root): bit-identical to the
+ *       reference for every tile size.
+ * A pivot <= 0 is the reference's "Not a symmetric positive definite (SPD)
+ * matrix" (sequential_cholesky.cpp:11-12): HCLIB_HIP_EDEVICE, the message
+ * holds that text and the column, result->fail_col is set and `l` is not
+ * written. Argument errors are HCLIB_HIP_EINVAL before the device is touched. */
+#define HCLIB_HIP_CHOL_EXACT 0   /* reference operation order, unfused: bit-identical to test/cholesky */
+typedef struct {
+    uint64_t tasks, puts, releases;        /* from the DAG launch */
+    uint64_t potrf, trsm, syrk, gemm;      /* tasks by kind */
+    double kernel_ms;                      /* device events around the one launch */
+    double gflops;                         /* (n^3/3) / kernel time */
+    int fail_col;                          /* -1, or the global column whose pivot was <= 0 */
+} hclib_hip_cholesky_result_t;
+int hclib_hip_cholesky(const double *a, int n, int tile, int mode, double *l,
+                       hclib_hip_cholesky_result_t *result);
 
 #ifdef __cplusplus
 }

@@ -36,7 +36,9 @@ namespace hx {
 constexpr uint32_t kDagEmpty = 0xffffffffu;
 constexpr uint32_t kDagSkip = 0xfffffffeu;  // a ready-list slot whose task its releaser ran
 
-enum : uint32_t { kErrDoublePut = 7 };
+// kErrNotSpd: a Cholesky pivot <= 0 (hclib_amd/csrc/cholesky.hip; the reference's
+// "Not a symmetric positive definite (SPD) matrix" exit, sequential_cholesky.cpp:11-12)
+enum : uint32_t { kErrDoublePut = 7, kErrNotSpd = 9 };
 
 // Device view of one DAG launch (hclib_hip_dag_launch_t, include/hclib_hip.h).
 struct DagView {
