@@ -90,6 +90,15 @@ class CholeskyResult(C.Structure):
                 ("kernel_ms", C.c_double), ("gflops", C.c_double), ("fail_col", C.c_int)]
 
 
+class SortResult(C.Structure):
+    """hclib_hip_sort_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("sort_leaf", C.c_uint64), ("sort_split", C.c_uint64),
+                ("merge_leaf", C.c_uint64), ("merge_split", C.c_uint64), ("merge_empty", C.c_uint64),
+                ("finishes", C.c_uint64), ("check_ins", C.c_uint64),
+                ("kernel_ms", C.c_double), ("keys_per_s", C.c_double)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -108,7 +117,7 @@ EXPORTS_HIP = [
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
-    "hclib_hip_forasync_reduce", "hclib_hip_cholesky",
+    "hclib_hip_forasync_reduce", "hclib_hip_cholesky", "hclib_hip_sort_i64", "hclib_hip_sort_bounds",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -173,6 +182,10 @@ def lib():
                                                 C.c_int, C.c_void_p]
         L.hclib_hip_cholesky.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
                                          C.POINTER(CholeskyResult)]
+        L.hclib_hip_sort_i64.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.POINTER(SortResult)]
+        L.hclib_hip_sort_bounds.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_sort_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_sort_last_ticks.restype = None
         _lib = L
     return _lib
 
@@ -513,6 +526,59 @@ def cholesky_format(L) -> str:
     the lower triangle, each value as "%lf " (six decimals), no newlines."""
     n = L.shape[0]
     return "".join("%f " % v for i in range(n) for v in L[i, :i + 1].tolist())
+
+
+# ---------------------------------------------------------------- BOTS sort
+def sort(keys, merge_cutoff: int = 2048, sort_cutoff: int = 2048):
+    """BOTS sort (cilksort) on dynamic device dataflow (hclib_hip_sort_i64):
+    keys is a one-dimensional array of int64; returns (the sorted keys as a new
+    int64 ndarray, stats). merge_cutoff / sort_cutoff are the reference's
+    cutoff_value / cutoff_value_1."""
+    import numpy as np
+
+    a = np.array(keys, dtype=np.int64, copy=True, order="C")
+    if a.ndim != 1:
+        raise ValueError("sort: keys must be one-dimensional")
+    r = SortResult()
+    _check(lib().hclib_hip_sort_i64(a.ctypes.data, a.shape[0], merge_cutoff, sort_cutoff, C.byref(r)),
+           "hclib_hip_sort_i64")
+    return a, {k: getattr(r, k) for k, _ in SortResult._fields_}
+
+
+def sort_bounds(n: int, merge_cutoff: int = 2048, sort_cutoff: int = 2048) -> dict:
+    """The pool sizes a sort of n keys allocates (hclib_hip_sort_bounds): upper
+    bounds on its device tasks, promises (finish scopes) and wait nodes."""
+    out = (C.c_uint64 * 3)()
+    _check(lib().hclib_hip_sort_bounds(n, merge_cutoff, sort_cutoff, out), "hclib_hip_sort_bounds")
+    return {"tasks": out[0], "promises": out[1], "wait_nodes": out[2]}
+
+
+def sort_last_ticks() -> dict:
+    """Wave time of the last sort() by task class, in ticks of the 100 MHz
+    device clock (hclib_hip_sort_last_ticks)."""
+    out = (C.c_uint64 * 6)()
+    lib().hclib_hip_sort_last_ticks(out)
+    return dict(zip(("sort_leaf", "sort_split", "merge_leaf", "merge_split", "merge_empty", "merge_phase"), out))
+
+
+def sort_bots_input(n: int):
+    """The reference's input (fill_array + scramble_array, sort.ref.c:425-446):
+    0 .. n-1, then for every i a swap with j = rand % n, rand the 64-bit LCG
+    rand * 1103515245 + 12345 (:93-97) from seed 1."""
+    import numpy as np
+
+    if n < 1:
+        raise ValueError("sort_bots_input: n must be positive")
+    # rand_i = a^i + c (1 + a + ... + a^(i-1)) mod 2^64 for seed 1: uint64
+    # arithmetic wraps, so both series come from cumulative operations
+    with np.errstate(over="ignore"):
+        pw = np.cumprod(np.full(n, 1103515245, dtype=np.uint64))
+        geo = np.cumsum(np.concatenate((np.ones(1, dtype=np.uint64), pw[:-1])))
+        js = ((pw + np.uint64(12345) * geo) % np.uint64(n)).tolist()
+    a = list(range(n))
+    for i, j in enumerate(js):
+        a[i], a[j] = a[j], a[i]
+    return np.array(a, dtype=np.int64)
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

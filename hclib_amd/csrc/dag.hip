@@ -267,6 +267,7 @@ struct DynState {
     DynView view{};
     void *arena = nullptr;
     size_t arena_bytes = 0;
+    unsigned long long finish[2] = {0, 0};  // the last launch's scopes opened, tasks checked in
 };
 DynState g_dyn;
 }  // namespace
@@ -358,12 +359,14 @@ extern "C" int hclib_hip_dyn_end(const char *who, hclib_hip_dyn_stats_t *stats) 
     HX_HIP(hipGetLastError());
     HX_HIP(hipEventRecord(m.ev1, m.stream));
     uint32_t ctl[512];
-    unsigned long long st[5] = {0, 0, 0, 0, 0};
+    unsigned long long st[7] = {0, 0, 0, 0, 0, 0, 0};
     HX_HIP(hipMemcpyAsync(ctl, v.ctl, sizeof(ctl), hipMemcpyDeviceToHost, m.stream));
     HX_HIP(hipMemcpyAsync(st, v.stats, sizeof(st), hipMemcpyDeviceToHost, m.stream));
     HX_HIP(hipStreamSynchronize(m.stream));
     float ms = 0;
     (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
+    g_dyn.finish[0] = st[5];
+    g_dyn.finish[1] = st[6];
     if (stats) {
         stats->tasks = st[0];
         stats->puts = st[1];
@@ -393,6 +396,11 @@ extern "C" int hclib_hip_dyn_end(const char *who, hclib_hip_dyn_stats_t *stats) 
         return HCLIB_HIP_EDEVICE;
     }
     return HCLIB_HIP_OK;
+}
+
+extern "C" void hclib_hip_dyn_finish_stats(uint64_t out[2]) {
+    out[0] = g_dyn.finish[0];
+    out[1] = g_dyn.finish[1];
 }
 
 extern "C" int hclib_hip_dyn_datum(uint32_t first, uint32_t n, uint64_t *datum, uint8_t *put) {

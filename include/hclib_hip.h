@@ -31,6 +31,11 @@
  *   hclib_hip_cholesky               the k-loop and its two finish scopes per step
  *                                    of test/cholesky/cholesky.cpp:80-124, with the
  *                                    four tile kernels, as one promise-DAG launch
+ *   hclib_hip_sort_i64               the spawns, the finish scopes with dynamic
+ *                                    check-in (src/hclib-runtime.c:431-446) and the
+ *                                    leaves of BOTS sort, test/performance-regression/
+ *                                    full-apps/bots/sort/sort.ref.c:315-423, as one
+ *                                    launch of dynamic device dataflow
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -474,6 +479,11 @@ int hclib_hip_dyn_begin(uint32_t payload_words, const uint32_t *root_payload, ui
                         uint32_t promise_cap, uint32_t node_cap, int waves_per_cu, uint32_t spin_limit_ms,
                         hclib_hip_dyn_launch_t *out);
 int hclib_hip_dyn_end(const char *who, hclib_hip_dyn_stats_t *stats);
+/* finish scopes of the last ended launch (hx::dyn_finish_open / _check_in /
+ * _check_out, the reference's finish counter with dynamic check-in,
+ * src/hclib-runtime.c:431-446): [0] scopes opened, [1] tasks added by
+ * check-ins */
+void hclib_hip_dyn_finish_stats(uint64_t out[2]);
 /* promises [first, first + n) of the last launch: data, and whether put */
 int hclib_hip_dyn_datum(uint32_t first, uint32_t n, uint64_t *datum, uint8_t *put);
 
@@ -542,6 +552,41 @@ typedef struct {
 } hclib_hip_cholesky_result_t;
 int hclib_hip_cholesky(const double *a, int n, int tile, int mode, double *l,
                        hclib_hip_cholesky_result_t *result);
+
+/* --------------------------------------------------------------- sort */
+/* BOTS sort (cilksort, test/performance-regression/full-apps/bots/sort:
+ * sort.ref.c:315-423, the HClib port sort.c) as ONE launch of dynamic device
+ * dataflow: one device task per call of the reference's call tree (four-way
+ * sort, binary-split merges), created on the device, its finish scopes as
+ * hx::dyn_finish_open / _check_in / _check_out, its leaves wave-wide HIP
+ * bodies. `keys` is a host array of n int64, sorted in place. merge_cutoff is
+ * the reference's cutoff_value (a merge whose smaller range holds at most
+ * that many keys is one task), sort_cutoff its cutoff_value_1 (fewer keys
+ * than that are sorted by one task, in LDS: at most 2048); 0 selects the
+ * reference's default, 2048. The reference's insertion cutoff has no device
+ * meaning. The empty-range copy moves all high1 - low1 + 1 keys (the
+ * reference's memcpy, sort.ref.c:344, is one short). The counts are those of
+ * the call tree, a function of the input alone. Argument errors are
+ * HCLIB_HIP_EINVAL before the device is touched: keys NULL, n < 1 or
+ * n >= 2^31, merge_cutoff < 2, sort_cutoff < 4 or > 2048.
+ * hclib_hip_sort_bounds: the pool sizes the launch allocates, upper bounds
+ * derived from n and the cutoffs for every input: out[0] tasks, out[1]
+ * promises (finish scopes), out[2] wait nodes. */
+typedef struct {
+    uint64_t tasks, sort_leaf, sort_split, merge_leaf, merge_split, merge_empty;
+    uint64_t finishes;      /* scopes opened */
+    uint64_t check_ins;     /* tasks added by dyn_finish_check_in */
+    double kernel_ms;       /* device events around the one launch */
+    double keys_per_s;
+} hclib_hip_sort_result_t;
+int hclib_hip_sort_i64(int64_t *keys, int64_t n, int merge_cutoff, int sort_cutoff,
+                       hclib_hip_sort_result_t *result);
+int hclib_hip_sort_bounds(int64_t n, int merge_cutoff, int sort_cutoff, uint64_t out[3]);
+/* Where the last sort's wave time went: ticks of the 100 MHz device clock
+ * summed over the tasks of each class, each from the start of its body to the
+ * end of its check-out: [0] sort leaves, [1] sort splits, [2] merge leaves,
+ * [3] merge splits, [4] empty-range copies, [5] merge-phase continuations. */
+void hclib_hip_sort_last_ticks(uint64_t out[6]);
 
 #ifdef __cplusplus
 }

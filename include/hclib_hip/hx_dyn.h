@@ -27,12 +27,25 @@
 // puts keep live above 0 and end in the bounded-spin timeout, the
 // reference's end_finish deadlock.
 //
+// Finish scopes (the reference's finish counter with dynamic check-in,
+// check_in_finish / check_out_finish, src/hclib-runtime.c:431-446, whose zero
+// puts the finish's promise, finish_dep of hclib_end_finish_nonblocking): a
+// scope is a promise whose datum word, free until the put, holds the count of
+// tasks checked in. dyn_finish_open creates it with a count, a task that is
+// itself checked in adds more with dyn_finish_check_in, every checked-in task
+// ends with dyn_finish_check_out, and the check-out that brings the count to
+// zero puts the promise through dyn_put, so tasks that dyn_async_await on the
+// scope are released like any other waiter.
+//
 // Memory protocol (hx_common.h; MI355X_MICROARCH.md "Valid forms"): payload
 // words, wait nodes and data are stored with agent-scope (sc1, write-through)
 // stores and drained before the atomic that publishes them; readers use
 // agent-scope loads. dyn_put<false> also releases at agent scope (a fence),
 // for tasks that wrote their outputs with plain stores; run_dyn_worker
-// acquires before a body unless Kind::kSc1Payload.
+// acquires before a body unless Kind::kSc1Payload. dyn_finish_check_out<false>
+// releases the same way before its decrement: the decrement that reaches zero
+// comes after every other one, so what every task of the scope wrote is out
+// before the put, and the waiter's acquire sees it.
 #pragma once
 
 #include "hx_common.h"
@@ -59,12 +72,14 @@ struct DynView {
     uint32_t *ctl;              // [0] head, [64] tail, [128] live, [192] err, [256] next task,
                                 // [320] next promise, [384] next wait node (one 256-B line each)
     unsigned long long *stats;  // [0] tasks run [1] puts [2] tasks created [3] releases [4] promises
+                                // [5] finish scopes opened [6] tasks added by dyn_finish_check_in
     uint32_t tcap, pcap, wcap, rcap, payload_words, spin_ms;
 };
 
 struct DynWave {
     DynView v;
     unsigned long long ran, puts, created, releases, promises;
+    unsigned long long finishes = 0, check_ins = 0;
 };
 
 __device__ __forceinline__ uint32_t *dyn_head(const DynView &v) { return v.ctl; }
@@ -218,12 +233,74 @@ __device__ __forceinline__ uint32_t dyn_async_await(DynWave &w, bool active, con
     return ok ? t : kDynEmpty;
 }
 
+// hclib_start_finish plus the `count` asyncs about to be spawned into it
+// (wave-uniform): a new promise, not put, whose datum word holds the count of
+// checked-in tasks. The count is stored write-through and drained here, ahead
+// of the creation of any task that could check out. kDynOpen when the promise
+// pool is exhausted (device error set).
+__device__ __forceinline__ uint32_t dyn_finish_open(DynWave &w, uint32_t count) {
+    const uint32_t f = dyn_promises(w, 1);
+    if (f != kDynOpen && lane_id() == 0) {
+        if (count == 0) dev_error(dyn_err(w.v), kErrBadTask);  // nothing could ever put it
+        st_agent(&w.v.datum[f], (unsigned long long)count);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    w.finishes += 1;
+    return f;
+}
+
+// check_in_finish, k tasks at once (wave-uniform). The caller is itself still
+// checked in to f, so the count is above zero before and after (a count of
+// zero here means it was not: a device error). The add has returned before
+// the caller can create the tasks it checks in.
+__device__ __forceinline__ void dyn_finish_check_in(DynWave &w, uint32_t f, uint32_t k) {
+    const DynView &v = w.v;
+    if (lane_id() == 0) {
+        if (f >= v.pcap) {
+            dev_error(dyn_err(v), kErrBadTask);
+        } else if (add_agent(&v.datum[f], (unsigned long long)k) == 0ull) {
+            dev_error(dyn_err(v), ld_agent(&v.phead[f]) == kDynPut ? kErrDynDoublePut : kErrBadTask);
+        }
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    w.check_ins += k;
+}
+
+// check_out_finish (wave-uniform): release what the task wrote (SC1: it wrote
+// what the scope's waiters read with agent-scope stores, so draining them is
+// the release), then one agent-scope decrement; the task that brings the count
+// to zero puts f, which releases the tasks that await it. A check-out of a
+// scope that is already put is the double put of dyn_put.
+template <bool SC1 = false>
+__device__ __forceinline__ void dyn_finish_check_out(DynWave &w, uint32_t f) {
+    const DynView &v = w.v;
+    if (SC1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    else release_agent();
+    uint32_t last = 0;
+    if (lane_id() == 0) {
+        if (f >= v.pcap) {
+            dev_error(dyn_err(v), kErrBadTask);
+        } else if (ld_agent(&v.phead[f]) == kDynPut) {
+            dev_error(dyn_err(v), kErrDynDoublePut);
+        } else {
+            const unsigned long long before = add_agent(&v.datum[f], ~0ull);
+            if (before == 0ull) dev_error(dyn_err(v), kErrDynDoublePut);  // more check-outs than check-ins
+            last = before == 1ull ? 1u : 0u;
+        }
+    }
+    last = (uint32_t)__builtin_amdgcn_readfirstlane((int)last);
+    // every other task of the scope released before its own decrement, which
+    // came before this one: nothing more to release here
+    if (last) dyn_put<true>(w, f, 0ull);
+}
+
 // Kind concept:
 //   struct Ctx;
 //   static constexpr bool kSc1Payload;  // bodies read other tasks' outputs only with agent-scope loads
 //   __device__ static void run(const Ctx&, DynWave&, uint32_t task, const uint32_t *payload);
 //        a wave-wide body; dyn_promises / dyn_put / dyn_get / dyn_async_await
-//        are wave-uniform calls (async_await one task per active lane).
+//        and dyn_finish_open / _check_in / _check_out are wave-uniform calls
+//        (async_await one task per active lane).
 template <class Kind>
 __device__ void run_dyn_worker(const typename Kind::Ctx &ctx, const DynView &view) {
     DynWave w{view, 0, 0, 0, 0, 0};
@@ -279,6 +356,8 @@ __device__ void run_dyn_worker(const typename Kind::Ctx &ctx, const DynView &vie
         add_agent(&view.stats[2], w.created);
         add_agent(&view.stats[3], w.releases);
         add_agent(&view.stats[4], w.promises);
+        if (w.finishes) add_agent(&view.stats[5], w.finishes);
+        if (w.check_ins) add_agent(&view.stats[6], w.check_ins);
     }
 }
 

@@ -659,6 +659,21 @@ int run_dag_groups(const typename Kind::Ctx &ctx, dag &g, hclib_hip_dag_stats_t 
 // (include/hclib_hip/hx_dyn.h); returns when every created task has run, or
 // HCLIB_HIP_EDEVICE (double put, pool exhausted, deadlock). dyn_datum reads
 // promises back afterwards.
+//
+// Finish scopes inside a Kind's body (wave-uniform calls, hx_dyn.h; the
+// reference's start_finish / check_in_finish / check_out_finish):
+//   f = hx::dyn_finish_open(w, count)    a promise, not put, with `count` tasks
+//                                        checked in: spawn them with f in their
+//                                        payload, and dyn_async_await the code
+//                                        after the finish with futs = {f}
+//   hx::dyn_finish_check_in(w, f, k)     a task that is itself checked in to f
+//                                        adds k more before it spawns them
+//   hx::dyn_finish_check_out<SC1>(w, f)  a checked-in task's last call: releases
+//                                        what it wrote (SC1 as in dyn_put) and
+//                                        decrements; the last one puts f. A task
+//                                        that hands its duty to a continuation
+//                                        passes f on and does not check out.
+// hclib_hip_dyn_finish_stats reads the scopes opened and the tasks checked in.
 struct dyn_caps {
     uint32_t tasks = 1u << 20, promises = 1u << 20, wait_nodes = 1u << 21;
     int waves_per_cu = 4;
