@@ -99,6 +99,15 @@ class SortResult(C.Structure):
                 ("kernel_ms", C.c_double), ("keys_per_s", C.c_double)]
 
 
+class SparseLUResult(C.Structure):
+    """hclib_hip_sparselu_result_t."""
+
+    _fields_ = [("blocks_in", C.c_uint64), ("blocks_out", C.c_uint64),
+                ("lu0", C.c_uint64), ("fwd", C.c_uint64), ("bdiv", C.c_uint64), ("bmod", C.c_uint64),
+                ("tasks", C.c_uint64), ("puts", C.c_uint64), ("releases", C.c_uint64),
+                ("kernel_ms", C.c_double), ("gflops", C.c_double), ("wgs_per_cu", C.c_int)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -118,6 +127,7 @@ EXPORTS_HIP = [
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
     "hclib_hip_forasync_reduce", "hclib_hip_cholesky", "hclib_hip_sort_i64", "hclib_hip_sort_bounds",
+    "hclib_hip_sparselu_genmat", "hclib_hip_sparselu_plan", "hclib_hip_sparselu", "hclib_hip_sparselu_bmod_rate",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -186,6 +196,13 @@ def lib():
         L.hclib_hip_sort_bounds.argtypes = [C.c_int64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.hclib_hip_sort_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
         L.hclib_hip_sort_last_ticks.restype = None
+        L.hclib_hip_sparselu_genmat.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hclib_hip_sparselu_plan.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.POINTER(C.c_uint64), C.c_void_p,
+                                              C.c_void_p, C.c_void_p]
+        L.hclib_hip_sparselu.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
+                                         C.POINTER(SparseLUResult)]
+        L.hclib_hip_sparselu_bmod_rate.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
+                                                   C.POINTER(C.c_double)]
         _lib = L
     return _lib
 
@@ -579,6 +596,100 @@ def sort_bots_input(n: int):
     for i, j in enumerate(js):
         a[i], a[j] = a[j], a[i]
     return np.array(a, dtype=np.int64)
+
+
+# ------------------------------------------------------------ BOTS SparseLU
+SPARSELU_KINDS = ("lu0", "fwd", "bdiv", "bmod")  # payload word 0 of a planned task
+
+
+def _slu_mask(mask):
+    import numpy as np
+
+    m = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    if m.ndim != 2 or m.shape[0] != m.shape[1]:
+        raise ValueError("sparselu: mask must be a square matrix of block flags")
+    return m
+
+
+def sparselu_genmat(S: int, B: int):
+    """The reference's generator (sparselu.ref.c:86-133, hclib_hip_sparselu_genmat):
+    (mask, blocks) with mask an S x S uint8 array and blocks the present blocks
+    in row-major (ii, jj) order, float32 of shape (count, B, B)."""
+    import numpy as np
+
+    if S < 1 or B < 1:
+        raise ValueError("sparselu_genmat: S and B must be positive")
+    mask = np.zeros((S, S), dtype=np.uint8)
+    _check(lib().hclib_hip_sparselu_genmat(S, B, mask.ctypes.data, None), "hclib_hip_sparselu_genmat")
+    blocks = np.empty((int(mask.sum()), B, B), dtype=np.float32)
+    _check(lib().hclib_hip_sparselu_genmat(S, B, mask.ctypes.data, blocks.ctypes.data), "hclib_hip_sparselu_genmat")
+    return mask, blocks
+
+
+def sparselu_plan(mask, graph: bool = True) -> dict:
+    """The symbolic pass of SparseLU on the host (hclib_hip_sparselu_plan; no
+    GPU): the final block structure after fill-in, the task counts and, with
+    graph=True, the promise DAG: payload (tasks x 4: kind, kk, ii, jj — the
+    task writes block (ii, jj)), await_off (tasks + 1) and await_ids, where
+    promise p is the one task p puts."""
+    import numpy as np
+
+    m = _slu_mask(mask)
+    S = m.shape[0]
+    out = np.zeros_like(m)
+    counts = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_sparselu_plan(m.ctypes.data, S, out.ctypes.data, counts, None, None, None),
+           "hclib_hip_sparselu_plan")
+    plan = {"mask_out": out, "blocks_in": counts[4], "blocks_out": counts[5], "tasks": sum(counts[:4])}
+    plan.update(zip(SPARSELU_KINDS, counts[:4]))
+    if graph:
+        n = plan["tasks"]
+        payload = np.zeros((n, 4), dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint32)
+        ids = np.zeros(3 * n, dtype=np.uint32)
+        _check(lib().hclib_hip_sparselu_plan(m.ctypes.data, S, None, None, payload.ctypes.data, off.ctypes.data,
+                                             ids.ctypes.data), "hclib_hip_sparselu_plan")
+        plan.update(payload=payload, await_off=off, await_ids=ids[:int(off[-1])].copy())
+    return plan
+
+
+def sparselu(mask, blocks, B: int):
+    """BOTS SparseLU on the device promise DAG (hclib_hip_sparselu): mask is an
+    S x S array of block flags, blocks the present blocks in row-major (ii, jj)
+    order (count x B x B float32). Returns (mask_out, blocks_out, stats):
+    the structure after fill-in and its blocks, L and U in place, bit-identical
+    to the reference's sparselu_seq_call. No pivoting and no pivot check."""
+    import numpy as np
+
+    m = _slu_mask(mask)
+    S = m.shape[0]
+    b = np.ascontiguousarray(blocks, dtype=np.float32)
+    if 1 <= B <= 128 and b.size != int(m.sum()) * B * B:
+        raise ValueError(f"sparselu: {int(m.sum())} present blocks of {B} x {B} need {int(m.sum()) * B * B} "
+                         f"floats, blocks holds {b.size}")
+    counts = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_sparselu_plan(m.ctypes.data, S, None, counts, None, None, None), "hclib_hip_sparselu_plan")
+    mask_out = np.zeros_like(m)
+    out = np.empty((counts[5], max(B, 0), max(B, 0)), dtype=np.float32)
+    r = SparseLUResult()
+    _check(lib().hclib_hip_sparselu(m.ctypes.data, b.ctypes.data, S, B, mask_out.ctypes.data, out.ctypes.data,
+                                    C.byref(r)), "hclib_hip_sparselu")
+    return mask_out, out, {k: getattr(r, k) for k, _ in SparseLUResult._fields_}
+
+
+def sparselu_bmod_rate(B: int, wgs_per_cu: int = 2, reps: int = 64):
+    """The bmod body alone on resident blocks (hclib_hip_sparselu_bmod_rate):
+    (kernel ms, GFLOP/s), the unfused f32 rate SparseLU's updates can reach."""
+    ms, gf = C.c_double(), C.c_double()
+    _check(lib().hclib_hip_sparselu_bmod_rate(B, wgs_per_cu, reps, C.byref(ms), C.byref(gf)),
+           "hclib_hip_sparselu_bmod_rate")
+    return ms.value, gf.value
+
+
+def sparselu_structure(mask) -> str:
+    """The reference's print_structure picture (sparselu.ref.c:141-148): one
+    line per block row, "x" for a present block and " " for an absent one."""
+    return "".join("".join("x" if v else " " for v in row) + "\n" for row in _slu_mask(mask).tolist())
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

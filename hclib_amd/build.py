@@ -27,7 +27,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
 SOURCES = ["module.hip", "forasync.hip", "uts.hip", "fib.hip", "sw.hip", "dag.hip", "hclib_api.hip", "locality.hip",
-           "calib.hip", "atomic.hip", "cholesky.hip", "sort.hip"]
+           "calib.hip", "atomic.hip", "cholesky.hip", "sort.hip", "sparselu.hip"]
 CFLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-result",
@@ -54,6 +54,8 @@ VARIANTS = {
     # compiler machine-scheduler strategies (within noise on T3L)
     "sched_minreg": ["-mllvm", "-amdgpu-sched-strategy=iterative-minreg"],
     "sched_ilp": ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"],
+    # SparseLU's bmod inner step kept off the packed f32 VALU (measured slower)
+    "slu_scalar": ["-DHX_SLU_SCALAR=1"],
     "base": [],
 }
 

@@ -36,6 +36,12 @@
  *                                    leaves of BOTS sort, test/performance-regression/
  *                                    full-apps/bots/sort/sort.ref.c:315-423, as one
  *                                    launch of dynamic device dataflow
+ *   hclib_hip_sparselu               the kk loop and its two finish barriers per step
+ *                                    of BOTS sparselu (bots/sparselu_single/
+ *                                    sparselu.c:331,348; sparselu.ref.c:300-322) with
+ *                                    its four block kernels, as one promise-DAG
+ *                                    launch whose graph a symbolic pass over the
+ *                                    block mask builds
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -130,6 +136,11 @@ int hclib_hip_last_timeline(uint64_t *out, uint64_t max_words, uint32_t *events_
 #define HCLIB_HIP_ATOMIC_HOT_WORD 1
 #define HCLIB_HIP_ATOMIC_COALESCED32 2
 int hclib_hip_atomic_calibrate(int mode, int iters, double *mops_per_s, double *kernel_ms);
+/* SparseLU calibration (not part of the factorisation's API): the bmod body of
+ * hclib_hip_sparselu alone, `reps` times per workgroup on resident B x B
+ * blocks, wgs_per_cu (1 or 2) workgroups per CU: kernel ms and the unfused f32
+ * rate (2 B^3 operations per bmod) the factorisation's updates can reach. */
+int hclib_hip_sparselu_bmod_rate(int B, int wgs_per_cu, int reps, double *ms, double *gflops);
 /* The chip's UTS SHA-1 issue ceiling: `chains` (1 or 2) independent rng_spawn
  * chains per lane (the instruction stream k_uts_search runs per node),
  * waves_per_cu waves on every CU, `iters` spawns per chain; SHA-1
@@ -587,6 +598,61 @@ int hclib_hip_sort_bounds(int64_t n, int merge_cutoff, int sort_cutoff, uint64_t
  * end of its check-out: [0] sort leaves, [1] sort splits, [2] merge leaves,
  * [3] merge splits, [4] empty-range copies, [5] merge-phase continuations. */
 void hclib_hip_sort_last_ticks(uint64_t out[6]);
+
+/* ----------------------------------------------------------- SparseLU */
+/* BOTS SparseLU (test/performance-regression/full-apps/bots/sparselu_single,
+ * sparselu_for: sparselu.ref.c:300-322, the HClib port sparselu.c) as ONE
+ * launch of the device promise DAG. The matrix is S x S blocks of B x B
+ * floats; mask[ii * S + jj] != 0 where block (ii, jj) is present. Blocks are
+ * block-packed: the present blocks in row-major (ii, jj) order, each B * B
+ * floats, row-major. The factorisation has no pivoting and creates blocks
+ * (fill-in, sparselu.ref.c:318), so the task graph depends on the mask:
+ *
+ * hclib_hip_sparselu_genmat  the reference's generator (sparselu.ref.c:86-133):
+ *     mask receives S * S bytes, blocks (unless NULL) the present blocks.
+ * hclib_hip_sparselu_plan    the symbolic pass, on the host alone: walks the
+ *     reference's program order over the mask, marks fill-in and builds the
+ *     graph. mask_out (S * S bytes, may be NULL) receives the final structure;
+ *     counts (may be NULL): [0] lu0 [1] fwd [2] bdiv [3] bmod tasks, [4] blocks
+ *     in, [5] blocks out. payload, await_off and await_ids (all three or none)
+ *     receive what hclib_hip_dag_begin takes: 4 words per task {kind (0 lu0,
+ *     1 fwd, 2 bdiv, 3 bmod), kk, ii, jj} — the task writes block (ii, jj) —
+ *     tasks + 1 await offsets, and at most 3 await ids per task (size them
+ *     from a first call's counts). Promise p is put by task p: a task awaits
+ *     the last writer of the block it updates and of each block it reads;
+ *     blocks nothing has written yet (the upload, a zeroed fill-in) need no
+ *     await. An absent diagonal block, S < 1 or more tasks than
+ *     hclib_hip_dag_begin accepts (2^32 - 2) are HCLIB_HIP_EINVAL; the tasks
+ *     are counted (on row bitsets) before any graph array is built, so the
+ *     limit costs no memory. A plan the host cannot hold is HCLIB_HIP_ENOMEM.
+ * hclib_hip_sparselu         the factorisation: host arrays in and out;
+ *     blocks_out is packed for mask_out ([5] of the plan's counts blocks) and
+ *     holds L (unit lower, below the diagonal) and U in place, as the
+ *     reference leaves them. Every element sees the reference's operations in
+ *     the reference's order (one rounded f32 multiply, one rounded f32
+ *     subtract, ascending k, IEEE divide): bit-identical to sparselu_seq_call
+ *     for every B. There is no pivot check, as in the reference: a zero pivot
+ *     gives inf / NaN and the call still returns HCLIB_HIP_OK. B < 1 or
+ *     B > 128 and the plan's errors are HCLIB_HIP_EINVAL before the device is
+ *     touched. Packing and both copies are outside kernel_ms.
+ *     gflops counts the reference's operations: a divide, and a multiply and
+ *     a subtract per update; per task lu0 B(B-1)/2 + (B-1)B(2B-1)/3,
+ *     fwd B^2 (B-1), bdiv B^3, bmod 2 B^3.
+ * (The calibration of the bmod body alone, hclib_hip_sparselu_bmod_rate, is
+ * with the other calibration entries above.) */
+typedef struct {
+    uint64_t blocks_in, blocks_out;        /* present blocks before and after (fill-in) */
+    uint64_t lu0, fwd, bdiv, bmod;         /* tasks by kind */
+    uint64_t tasks, puts, releases;        /* from the DAG launch */
+    double kernel_ms;                      /* device events around the one launch */
+    double gflops;                         /* the reference's operations / kernel time */
+    int wgs_per_cu;                        /* persistent workgroups per CU of the launch */
+} hclib_hip_sparselu_result_t;
+int hclib_hip_sparselu_genmat(int S, int B, uint8_t *mask, float *blocks);
+int hclib_hip_sparselu_plan(const uint8_t *mask, int S, uint8_t *mask_out, uint64_t counts[6],
+                            uint32_t *payload, uint32_t *await_off, uint32_t *await_ids);
+int hclib_hip_sparselu(const uint8_t *mask, const float *blocks, int S, int B,
+                       uint8_t *mask_out, float *blocks_out, hclib_hip_sparselu_result_t *result);
 
 #ifdef __cplusplus
 }
