@@ -108,6 +108,14 @@ class SparseLUResult(C.Structure):
                 ("kernel_ms", C.c_double), ("gflops", C.c_double), ("wgs_per_cu", C.c_int)]
 
 
+class NQueensResult(C.Structure):
+    """hclib_hip_nqueens_result_t."""
+
+    _fields_ = [("solutions", C.c_uint64), ("tasks", C.c_uint64), ("items", C.c_uint64), ("scopes", C.c_uint64),
+                ("joins", C.c_uint64), ("chunks_pushed", C.c_uint64), ("chunks_stolen", C.c_uint64),
+                ("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -128,6 +136,7 @@ EXPORTS_HIP = [
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
     "hclib_hip_forasync_reduce", "hclib_hip_cholesky", "hclib_hip_sort_i64", "hclib_hip_sort_bounds",
     "hclib_hip_sparselu_genmat", "hclib_hip_sparselu_plan", "hclib_hip_sparselu", "hclib_hip_sparselu_bmod_rate",
+    "hclib_hip_nqueens", "hclib_hip_nqueens_bounds",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -203,6 +212,8 @@ def lib():
                                          C.POINTER(SparseLUResult)]
         L.hclib_hip_sparselu_bmod_rate.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
                                                    C.POINTER(C.c_double)]
+        L.hclib_hip_nqueens.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(NQueensResult), C.POINTER(C.c_uint64)]
+        L.hclib_hip_nqueens_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -690,6 +701,41 @@ def sparselu_structure(mask) -> str:
     """The reference's print_structure picture (sparselu.ref.c:141-148): one
     line per block row, "x" for a present block and " " for an absent one."""
     return "".join("".join("x" if v else " " for v in row) + "\n" for row in _slu_mask(mask).tolist())
+
+
+# ---------------------------------------------------------------- N-Queens
+NQUEENS_FORMS = {"bots": 0, "flat": 1}  # HCLIB_HIP_NQUEENS_BOTS / _FLAT
+
+
+def _nqueens_form(form) -> int:
+    if form not in NQUEENS_FORMS:
+        raise ValueError(f"nqueens: form {form!r} is not one of {sorted(NQUEENS_FORMS)}")
+    return NQUEENS_FORMS[form]
+
+
+def nqueens(n: int, form: str = "bots", task_depth: int = 0, hist: bool = False) -> dict:
+    """N-Queens on the work-stealing scheduler (hclib_hip_nqueens): form "bots"
+    (one finish scope per call, sums climbing the scopes) or "flat" (a task per
+    valid placement, one counter). task_depth is the BOTS cutoff: calls at that
+    depth and below are finished by one lane's serial search; 0 = every call
+    spawns. Returns the fields of hclib_hip_nqueens_result_t and, with hist,
+    "hist": the number of valid prefixes of each length 0..n."""
+    r = NQueensResult()
+    h = (C.c_uint64 * (max(n, 0) + 1))() if hist else None
+    _check(lib().hclib_hip_nqueens(n, _nqueens_form(form), task_depth, C.byref(r), h), "hclib_hip_nqueens")
+    out = {k: getattr(r, k) for k, _ in NQueensResult._fields_}
+    if hist:
+        out["hist"] = list(h)
+    return out
+
+
+def nqueens_bounds(n: int, form: str = "bots", task_depth: int = 0) -> dict:
+    """The reference's task and finish-scope counts for (n, form, task_depth),
+    on the host alone (hclib_hip_nqueens_bounds); scopes is what the BOTS
+    form's arena is sized from."""
+    out = (C.c_uint64 * 2)()
+    _check(lib().hclib_hip_nqueens_bounds(n, _nqueens_form(form), task_depth, out), "hclib_hip_nqueens_bounds")
+    return {"tasks": out[0], "scopes": out[1]}
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

@@ -42,6 +42,11 @@
  *                                    its four block kernels, as one promise-DAG
  *                                    launch whose graph a symbolic pass over the
  *                                    block mask builds
+ *   hclib_hip_nqueens                the asyncs, the finish per call and the csols[]
+ *                                    sums of BOTS nqueens (bots/nqueens/nqueens.c:
+ *                                    125-182), and the flat form's asyncs and counter
+ *                                    (full-apps/nqueens.cpp:41-60), as task kinds of
+ *                                    the work-stealing megakernel
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -653,6 +658,49 @@ int hclib_hip_sparselu_plan(const uint8_t *mask, int S, uint8_t *mask_out, uint6
                             uint32_t *payload, uint32_t *await_off, uint32_t *await_ids);
 int hclib_hip_sparselu(const uint8_t *mask, const float *blocks, int S, int B,
                        uint8_t *mask_out, float *blocks_out, hclib_hip_sparselu_result_t *result);
+
+/* ------------------------------------------------------------ N-Queens */
+/* N-Queens on the persistent work-stealing scheduler (the one fib and UTS run
+ * on), in the reference's two forms:
+ *   HCLIB_HIP_NQUEENS_BOTS  test/performance-regression/full-apps/bots/nqueens/
+ *       nqueens.c:125-182: every call nqueens(n, j, a) with j < n opens a finish
+ *       scope and spawns its column tasks; the counts are summed up the scopes
+ *       (`*solutions += csols[i]`), the root scope's value is the answer.
+ *   HCLIB_HIP_NQUEENS_FLAT  test/performance-regression/full-apps/nqueens.cpp:
+ *       41-60 (and test/misc/nqueens.cpp): one outer finish, an async only for a
+ *       placement that passes ok(), one counter (here: one per lane, summed).
+ * task_depth is the BOTS manual cutoff: a call with j >= task_depth is finished
+ * by one lane's serial search (nqueens_ser); 0, or anything >= n, means every
+ * call spawns, as both HClib ports do.
+ * result->solutions is the count. tasks and scopes are the reference's: with
+ * P(n, j) = the valid prefixes of j queens and m = the effective task depth,
+ * BOTS scopes = the sum of P(n, j) over j < m (one finish per spawning call) and
+ * tasks = n * scopes (its n asyncs); flat tasks = the sum of P(n, j) over
+ * 1 <= j <= m, scopes = 0. items is what the device ran: in the BOTS form the
+ * parent settles a conflicting placement itself (the scope counts the free
+ * columns only, and a call with no free column closes at once on a sum of zero
+ * without a scope of its own), so items is far below tasks; both include the
+ * root item, which stands for the call nqueens(n, 0). joins = scopes closed.
+ * hist (n + 1 entries, or NULL): hist[j] = P(n, j), counted by the tasks and by
+ * the lanes' serial searches alike (a separate kernel instantiation).
+ * HCLIB_HIP_EINVAL before the device is touched: n < 1 or n > 20, a form that
+ * is neither of the two, task_depth < 0, result NULL, and in the BOTS form a
+ * scope count above what the arena can address (0xfffffff0 less the 2^24 ids
+ * reserved for the workers' id blocks). The BOTS arena holds every scope once;
+ * its exact size is a depth-first search on the host, outside kernel_ms.
+ * hclib_hip_nqueens_bounds: host only, no GPU: out[0] tasks, out[1] scopes as
+ * above for (n, form, task_depth), with the same argument checks (in the flat
+ * form the count walks every prefix up to the task depth: the whole search
+ * when every call spawns). */
+typedef struct {
+    uint64_t solutions, tasks, items, scopes, joins, chunks_pushed, chunks_stolen;
+    double kernel_ms, busy_frac;
+} hclib_hip_nqueens_result_t;
+#define HCLIB_HIP_NQUEENS_BOTS 0
+#define HCLIB_HIP_NQUEENS_FLAT 1
+int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nqueens_result_t *result,
+                      uint64_t *hist /* n + 1 entries, may be NULL */);
+int hclib_hip_nqueens_bounds(int n, int form, int task_depth, uint64_t out[2]);
 
 #ifdef __cplusplus
 }
