@@ -434,6 +434,15 @@ static int geo_n(double prob, uint32_t h) {
     return cvt_int_x86(floor(log(1 - u) / log(1 - prob)));
 }
 
+// The children of a BIN-rule node that spawns (uts.c:162-168 return m; the
+// caller, uts.c:225-274, then truncates every node but a BIN root and every
+// tree but BALANCED to MAXNUMCHILDREN = 100, uts.h:31): -m above 100 gives
+// 100 children, on the device (UtsCtx::m) and in the host mirror (host_nc)
+constexpr int kUtsMaxChildren = 100;
+static int bin_rule_m(const hclib_hip_uts_params_t &p) {
+    return p.non_leaf_bf > kUtsMaxChildren ? kUtsMaxChildren : p.non_leaf_bf;
+}
+
 // Expected node count of a GEO / HYBRID tree (sum over depths of the product
 // of the mean branching factors above it) — a launch-shape heuristic only:
 // T1 1.4 M, T2 0.8 M, T4 3.3 M, T5 3.8 M, T1L 89 M, T2L 184 M
@@ -442,7 +451,7 @@ static double uts_expected_nodes(const hclib_hip_uts_params_t &p) {
     for (int d = 0; d < 10 * p.gen_mx + 10 && prod > 1e-9 && tot < 1e13; ++d) {
         tot += prod;
         const bool bin_level = p.type == 0 ? d > 0 : (p.type == 2 && d >= p.shift_depth * p.gen_mx);
-        const double mu = bin_level ? p.non_leaf_prob * p.non_leaf_bf : geo_bi(p, d);
+        const double mu = bin_level ? p.non_leaf_prob * bin_rule_m(p) : geo_bi(p, d);
         prod *= mu > 0.0 ? mu : 0.0;
     }
     return tot;
@@ -635,7 +644,7 @@ static int host_nc(const hclib_hip_uts_params_t &p, const UtsTables &T, int d, u
     int ri = d < (int)T.rules.size() ? d : (int)T.rules.size() - 1;
     int4 rule = T.rules[ri];
     if (rule.x == 0) return rule.y;
-    if (rule.x == 1) return r < (uint32_t)rule.y ? p.non_leaf_bf : 0;
+    if (rule.x == 1) return r < (uint32_t)rule.y ? bin_rule_m(p) : 0;
     int n = 0;
     for (int k = 1; k <= 100; ++k) n += T.thr[(size_t)rule.z * 128 + k] <= r;
     return n;
@@ -797,7 +806,7 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     ctx.nrules = (int)T.rules.size();
     ctx.stationary = T.stationary;
     ctx.gran = params->compute_gran < 1 ? 1 : params->compute_gran;
-    ctx.m = params->non_leaf_bf;
+    ctx.m = bin_rule_m(*params);  // read by BIN rules only (BIN and HYBRID trees), capped at 100
     ctx.shard = shard;
     ctx.nshards = nshards;
     ctx.split = split_depth;
@@ -855,8 +864,10 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // below the split the filter executes nothing: the FEAT = 1 body
     // compiles the span-bound narrow loop worse (the FEAT = 0 kernel on the
     // same shard: +0.05-0.14 ms; profiles/r06/shard_big_a.log)
-    const bool bin_seed = bin && nshards > 1 && !global && max_levels == 0 && split_depth >= 1 &&
-                          split_depth + 1 < kSeedMaxLevels && env_int("HCLIB_HIP_UTS_SEED", 1);
+    // (... where the levels fit the seeding's buffers: the fit test below,
+    // once the grid is known)
+    bool bin_seed = bin && nshards > 1 && !global && max_levels == 0 && split_depth >= 1 &&
+                    split_depth + 1 < kSeedMaxLevels && env_int("HCLIB_HIP_UTS_SEED", 1);
     // BIN trees: four worker waves per CU in one workgroup (one per SIMD;
     // three siblings to hand work to through LDS before the HBM deques):
     // T3L 29.08 -> 28.76 ms mean of 6 interleaved rounds against two per CU
@@ -887,6 +898,34 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     const int grid = env_int("HCLIB_HIP_GRID", 0) > 0
                          ? env_int("HCLIB_HIP_GRID", 0)
                          : m.num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", wpc_default);
+    // a knob value that cannot fit the ring is refused here, before the
+    // launch (as check_resident refuses a grid that cannot be resident),
+    // instead of ending in a device error after it
+    auto refuse = [&]() {
+        if (dmem) (void)hipFree(dmem);
+        if (d_chain) (void)hipFree(d_chain);
+        return HCLIB_HIP_EINVAL;
+    };
+    if (bin_seed) {
+        // the seeding's fit test, as the fixed-shape one below: level d holds
+        // the slots of depth d + 1, expected n(1) = the root's children and
+        // n(d) = n(1) (q m)^(d - 1) below. The unfiltered levels (depths 1 ..
+        // split) and this shard's part of depth split + 1 stay within half
+        // the level buffer (8 x target + 65,536 slots at target = 1: wave 0
+        // also truncates a root wider than the buffer), and a wave's share of
+        // that last level within a quarter of its 1,024-item ring on this
+        // grid (seed_levels refuses more than half). Otherwise the worker
+        // loop filters (FEAT = 1), which needs no level buffers.
+        const double cap = 8.0 * 1 + 65536.0;
+        const double qm = params->non_leaf_prob * bin_rule_m(*params) > 0 ? params->non_leaf_prob * bin_rule_m(*params) : 0.0;
+        double n = T.root_nc > 0 ? (double)T.root_nc : 0.0, widest = n;
+        for (int d = 2; d <= split_depth; ++d) {
+            n *= qm;
+            if (n > widest) widest = n;
+        }
+        const double n_mine = n * qm / nshards;
+        if (!(widest <= 0.5 * cap && n_mine <= 0.5 * cap && n_mine <= (double)grid * (1024 / 4))) bin_seed = false;
+    }
     SchedConfig cfg;
     cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_SPILL_HI", 512);
     // BIN trees with the narrow-frontier loop give work away from 72 items
@@ -898,6 +937,11 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // at one piece per task (T1XL 37.2 ms, T1L 3.77; profiles/r02/
     // pieces_tune.log; 336 at five pieces), 128 on 256-item rings (T1)
     const int ring_used = geo_fixed && !(nshards > 1 || max_levels > 0) ? env_int("HCLIB_HIP_UTS_RING", ring_default) : 512;
+    if (ring_used != 256 && ring_used != 512 && ring_used != 1024) {
+        set_error("hclib_hip_uts_search: HCLIB_HIP_UTS_RING=%d is not a ring the search is built for (256, 512 or 1024 "
+                  "items per wave)", ring_used);
+        return refuse();
+    }
     // BIN trees: 66 since the register carry went through LDS (T3L 30.64 ->
     // 30.20 ms same-box against 72, profiles/r04/sc_ab_t3l*.log, t3l3_spill.log);
     // it must stay above one batch (64) or the narrow loop never runs
@@ -906,8 +950,65 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // keeps more before it feeds others: T1 0.285 -> 0.248 ms at 336, T1L
     // 2.70 -> 2.38, T1XL's 8-way shards 4.94 -> 4.75 at 448
     // (profiles/r04/seed5_*.log, seed6_*.log)
-    const bool seeded = seed_on && ring_used >= 512;
+    // slots per wave: a few for a small tree (one level fewer to expand),
+    // more for a large one (finer shares, less stealing later;
+    // profiles/r04/seed3_*.log, seed4_*.log)
+    // (16 for small trees since round 5: one level deeper, T1 0.234 ->
+    // 0.220 ms, profiles/r05/sweep_t1_d.log; a level holds at most ~b x
+    // the target, so 32 keeps a wave's share of a b = 4 level within
+    // half its ring)
+    const int per_wave = env_int("HCLIB_HIP_SEED_PER_WAVE", uts_expected_nodes(*params) >= 3e7 ? 32 : 16);
+    bool seed_fits = seed_on && ring_used >= 512;
+    if (seed_fits) {
+        // the seeding stops at the first level of at least the target, which
+        // the level before it (below the target) reaches b-fold: a wave's
+        // share comes to b x per_wave items, and seed_levels takes at most
+        // half a ring. A knob value past that is refused (the defaults are
+        // measured shapes and stay as they are)
+        if (getenv("HCLIB_HIP_SEED_PER_WAVE")) {
+            const double b = geo_bi(*params, 1) > kUtsMaxChildren ? (double)kUtsMaxChildren : geo_bi(*params, 1);
+            if (per_wave < 1) {
+                set_error("hclib_hip_uts_search: HCLIB_HIP_SEED_PER_WAVE=%d is not a slot count (1 or more; "
+                          "HCLIB_HIP_UTS_SEED=0 turns the seeding off)", per_wave);
+                return refuse();
+            }
+            if (b * per_wave > ring_used / 2) {
+                set_error("hclib_hip_uts_search: HCLIB_HIP_SEED_PER_WAVE=%d cannot fit the ring: a wave's share of the "
+                          "seeded level reaches %.0f x %d items, the seeding hands over at most %d of a %d-item ring",
+                          per_wave, b, per_wave, ring_used / 2, ring_used);
+                return refuse();
+            }
+        }
+        // ... and the launch is seeded only where that level fits, by the
+        // expected level sizes n(1) = the root's children, n(d + 1) = n(d) b_d:
+        // the first level of at least the target within half the level
+        // buffer (8 x target + 65,536 slots) and a wave's share of it within
+        // a quarter of its ring, on this grid. (Always so at b = 4 with the
+        // default slots per wave; not for a wide tree on a small grid: b = 40
+        // on 4 waves passes a 63-slot level, one short of the target, and
+        // shares out the 2,177 slots of the next.) A tree that ends below the
+        // target is expanded by the seeding alone. Otherwise the search
+        // starts unseeded, from the root.
+        const double target = (double)grid * per_wave, cap = 8.0 * target + 65536.0;
+        double n = T.root_nc > 0 ? (double)T.root_nc : 0.0;
+        for (int d = 1; d < 64 && n > 0.0 && n < target; ++d) {
+            const double b = geo_bi(*params, d) > kUtsMaxChildren ? (double)kUtsMaxChildren : geo_bi(*params, d);
+            n *= b > 0.0 ? b : 0.0;
+        }
+        seed_fits = n <= 0.5 * cap && n <= (double)grid * (ring_used / 4);
+    }
+    const bool seeded = seed_fits;
     if (seeded) spill_lo_default = uts_expected_nodes(*params) >= 3e7 ? 448 : 336;
+    {
+        // a wave never holds more than its ring: a threshold past it would
+        // keep every wave from ever feeding a hungry one
+        const int ring_launch = bin ? 1024 : ring_used, lo = env_int("HCLIB_HIP_SPILL_LO", spill_lo_default);
+        if (lo < 1 || lo > ring_launch) {
+            set_error("hclib_hip_uts_search: HCLIB_HIP_SPILL_LO=%d does not fit the %d-item ring of this launch "
+                      "(1..%d)", lo, ring_launch, ring_launch);
+            return refuse();
+        }
+    }
     cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_SPILL_LO", spill_lo_default);
     cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
     cfg.nwaves = (uint32_t)grid;
@@ -943,14 +1044,6 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // of growing the busy set from one root by hand-offs
     SeedCfg seed{0, 0, (uint32_t)UtsKind<kUtsBin, 0>::kWords, 0};
     if (seeded) {
-        // slots per wave: a few for a small tree (one level fewer to expand),
-        // more for a large one (finer shares, less stealing later;
-        // profiles/r04/seed3_*.log, seed4_*.log)
-        // (16 for small trees since round 5: one level deeper, T1 0.234 ->
-        // 0.220 ms, profiles/r05/sweep_t1_d.log; a level holds at most ~b x
-        // the target, so 32 keeps a wave's share of a b = 4 level within
-        // half its ring)
-        const int per_wave = env_int("HCLIB_HIP_SEED_PER_WAVE", uts_expected_nodes(*params) >= 3e7 ? 32 : 16);
         seed.target = (uint32_t)(grid * per_wave);
         seed.max_levels = (uint32_t)env_int("HCLIB_HIP_SEED_LEVELS", 20);
         // wave 0 alone runs the levels of at most 128 slots (its ring's room

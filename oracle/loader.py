@@ -76,10 +76,29 @@ def parse_uts_args(argv: str) -> UtsParams:
 _libs: dict = {}
 
 
+# the newest entry point each library must export: a library built from an
+# older source (a kept _build/ directory) is rebuilt instead of failing at the
+# first call of a symbol it lacks
+_NEWEST_SYMBOL = {"liboracle.so": b"ora_uts_serial_shard", "libhclib_cpu.so": b"ora_uts_serial_shard"}
+_checked = False
+
+
+def _has_symbol(path: str, name: bytes) -> bool:
+    try:
+        with open(path, "rb") as f:
+            return name in f.read()
+    except OSError:
+        return False
+
+
 def ensure_built() -> None:
-    if not (os.path.exists(os.path.join(BUILD, "liboracle.so"))
-            and os.path.exists(os.path.join(BUILD, "libhclib_cpu.so"))):
-        subprocess.check_call(["make", "-s", "-C", HERE, "all"])
+    global _checked
+    if _checked:
+        return
+    if not all(_has_symbol(os.path.join(BUILD, so), sym) for so, sym in _NEWEST_SYMBOL.items()):
+        # -B: the libraries are stale whatever their timestamps say
+        subprocess.check_call(["make", "-s", "-B", "-C", HERE, "all"])
+    _checked = True
 
 
 def _load(name: str, path: str):
@@ -120,6 +139,17 @@ def uts_serial(p: UtsParams, max_levels: int = 0):
     hist = (C.c_uint64 * max_levels)() if max_levels else None
     rc = lib.ora_uts_serial(C.byref(p), C.byref(r), hist, max_levels)
     assert rc == 0
+    return (r.nodes, r.leaves, r.max_depth), (list(hist) if hist is not None else None)
+
+
+def uts_serial_shard(p: UtsParams, shard: int, nshards: int, split: int, max_levels: int = 0):
+    """One shard of the state-hash partition (ora_uts_serial_shard): the
+    counts this shard reports, and its per-level histogram."""
+    lib = oracle()
+    r = UtsResult()
+    hist = (C.c_uint64 * max_levels)() if max_levels else None
+    rc = lib.ora_uts_serial_shard(C.byref(p), shard, nshards, split, C.byref(r), hist, max_levels)
+    assert rc == 0, rc
     return (r.nodes, r.leaves, r.max_depth), (list(hist) if hist is not None else None)
 
 

@@ -194,16 +194,31 @@ static int stack_push(ora_stack_t *s, const ora_node_t *x) {
     return 0;
 }
 
-/* genChildren + ss_get_work loop (UTS.cpp:154-232, 383-402) on one worker. */
+/* genChildren + ss_get_work loop (UTS.cpp:154-232, 383-402) on one worker.
+ * nshards > 1 restricts the walk to one shard of the multi-GPU partition
+ * (not part of the reference): the levels above `split`
+ * are expanded by every shard and counted by shard 0 alone, a node at height
+ * == split belongs to shard st[0] % nshards (st[0]: the first digest word,
+ * bytes 0..3 of the reference's state, big-endian) and is dropped by every
+ * other shard, neither counted nor expanded; all below an owned node counts. */
 static int dfs(const ora_uts_params_t *p, ora_stack_t *s, ora_uts_result_t *out,
-               uint64_t *hist, int max_levels) {
+               uint64_t *hist, int max_levels, int shard, int nshards, int split) {
     while (s->n) {
         ora_node_t parent = s->v[--s->n];
-        out->nodes++;
-        if (hist && parent.height < max_levels) hist[parent.height]++;
-        if ((uint64_t)parent.height > out->max_depth) out->max_depth = parent.height;
+        int counted = 1;
+        if (nshards > 1) {
+            if (parent.height == split && parent.st[0] % (uint32_t)nshards != (uint32_t)shard)
+                continue;
+            if (parent.height < split && shard != 0) counted = 0;
+        }
         int nc = ora_uts_num_children(p, parent.type, parent.height, parent.st);
         int ct = ora_uts_child_type(p, parent.height);
+        if (counted) {
+            out->nodes++;
+            if (hist && parent.height < max_levels) hist[parent.height]++;
+            if ((uint64_t)parent.height > out->max_depth) out->max_depth = parent.height;
+            if (nc <= 0) out->leaves++;
+        }
         if (nc > 0) {
             for (int i = 0; i < nc; i++) {
                 ora_node_t child;
@@ -212,8 +227,6 @@ static int dfs(const ora_uts_params_t *p, ora_stack_t *s, ora_uts_result_t *out,
                 for (int g = 0; g < p->compute_gran; g++) ora_rng_spawn(parent.st, child.st, i);
                 if (stack_push(s, &child)) return -1;
             }
-        } else {
-            out->leaves++;
         }
     }
     return 0;
@@ -221,6 +234,12 @@ static int dfs(const ora_uts_params_t *p, ora_stack_t *s, ora_uts_result_t *out,
 
 int ora_uts_serial(const ora_uts_params_t *p, ora_uts_result_t *out, uint64_t *hist,
                    int max_levels) {
+    return ora_uts_serial_shard(p, 0, 1, 0, out, hist, max_levels);
+}
+
+int ora_uts_serial_shard(const ora_uts_params_t *p, int shard, int nshards, int split,
+                         ora_uts_result_t *out, uint64_t *hist, int max_levels) {
+    if (nshards < 1 || shard < 0 || shard >= nshards || (nshards > 1 && split < 1)) return -2;
     ora_stack_t s = {0};
     ora_node_t root;
     memset(out, 0, sizeof(*out));
@@ -230,7 +249,7 @@ int ora_uts_serial(const ora_uts_params_t *p, ora_uts_result_t *out, uint64_t *h
     root.height = 0;
     ora_rng_init(root.st, p->root_id);
     if (stack_push(&s, &root)) return -1;
-    int rc = dfs(p, &s, out, hist, max_levels);
+    int rc = dfs(p, &s, out, hist, max_levels, shard, nshards, split);
     free(s.v);
     return rc;
 }
@@ -256,7 +275,7 @@ int ora_uts_serial_root_range(const ora_uts_params_t *p, int first, int last, in
         ora_rng_spawn(root.st, child.st, i);
         if (stack_push(&s, &child)) return -1;
     }
-    int rc = dfs(p, &s, out, NULL, 0);
+    int rc = dfs(p, &s, out, NULL, 0, 0, 1, 0);
     free(s.v);
     return rc;
 }

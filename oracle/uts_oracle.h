@@ -71,6 +71,16 @@ int ora_uts_child_type(const ora_uts_params_t *p, int height); /* uts.c:277-294 
 int ora_uts_serial(const ora_uts_params_t *p, ora_uts_result_t *out,
                    uint64_t *level_hist, int max_levels);
 
+/* One shard of the multi-GPU partition, walked
+ * serially: every shard expands the levels above `split`, whose nodes
+ * (height < split) only shard 0 counts — nodes, leaves, depth and histogram;
+ * a node at height == split belongs to shard st[0] % nshards and is dropped
+ * by the others, neither counted nor expanded; everything below an owned
+ * node is counted. nshards == 1 is ora_uts_serial. Returns 0 on success,
+ * -2 on arguments the device entry point refuses as well. */
+int ora_uts_serial_shard(const ora_uts_params_t *p, int shard, int nshards, int split,
+                         ora_uts_result_t *out, uint64_t *level_hist, int max_levels);
+
 /* Serial walk of the subtrees rooted at the children [first, last) of the
  * root only (used for multi-rank sharding checks). The root itself is
  * counted iff count_root != 0. */
