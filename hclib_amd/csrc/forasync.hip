@@ -305,7 +305,8 @@ extern "C" int hclib_hip_forasync_triad_f32(float *a, const float *b, const floa
         // non-temporal stores: 6.22-6.26 TB/s, against 6.15-6.22 for one
         // workgroup with two pairs; the LDS-DMA form (variants 256-263) and
         // deeper pipelines measured no faster
-        const int bpc = env_int("HCLIB_HIP_TRIAD_BLOCKS_PER_CU", 2);
+        int bpc = env_int("HCLIB_HIP_TRIAD_BLOCKS_PER_CU", 2);
+        if (bpc < 1) bpc = 1;  // 0 or less would ask for an empty grid
         int threads = kTriadThreads;
         triad_kernel_t k = triad_variant(env_int("HCLIB_HIP_TRIAD_VARIANT", 131), &threads);
         int64_t grid = (int64_t)mod().num_cus * bpc;

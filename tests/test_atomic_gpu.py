@@ -8,7 +8,12 @@ hclib_hip_atomic_* and hclib_hip_forasync_reduce in include/hclib_hip.h).
 (b) hclib_amd.forasync_reduce against numpy. Float inputs are integer-valued
     in [0, 15]: every partial sum stays below 2^24 at n <= 2^20 + 1, so the
     sum is exact in any order and compared with ==.
-(c) a float sum of random values is bit-identical from run to run."""
+(c) a float sum of random values is bit-identical from run to run.
+(d) the unrolled forms of the contiguous sweep (HCLIB_HIP_REDUCE_UNROLL 2, 4,
+    8 beside the default 1) at one workgroup per CU, at the counts where the
+    unrolled loop is just missed, just filled and run twice before a partial
+    remainder stride; the sum against numpy, and max with its maximum at one
+    position per launch, so a kernel that skips a region fails."""
 import os
 import subprocess
 
@@ -188,3 +193,127 @@ def test_float_sum_is_bit_reproducible():
             got.append(np.float32(a.gather()).tobytes())
     assert got[0] == got[1]
     assert np.isfinite(np.frombuffer(got[0], np.float32)[0])
+
+
+# ------------------------------------------------ unrolled contiguous sweep
+UNROLLS = [1, 2, 4, 8]
+UNROLL_DTYPES = ["int32", "float32", "float64"]
+MAX_CONST, MAX_PEAK = 3, 7
+
+
+def _vec(dt):
+    return 16 // np.dtype(dt).itemsize  # elements per 16-byte vector
+
+
+def _unroll_counts(st, N, U):
+    """k_reduce_contig at one workgroup per CU strides st = G * 256 vectors of N
+    elements: lane i sums vectors i, i + st, ..., U at a time while
+    i + (U - 1) st < nv, then one at a time. U st N - 1 leaves the last lane out
+    of the unrolled loop, U st N fills it exactly once, U st N + 1 adds a tail
+    element (or, after a head, one more vector); 2 U st N + st N + 131 runs it
+    twice, then a whole remainder stride, then 131 / N more vectors and a tail."""
+    return [U * st * N - 1, U * st * N, U * st * N + 1, 2 * U * st * N + st * N + 131]
+
+
+@pytest.fixture(scope="module")
+def big():
+    """Integer-valued inputs for the largest count (U = 8) plus the offset
+    element, on the host (with exact prefix sums) and on the device. Values lie
+    in [0, hi] with hi * count < 2^24, so every float32 partial sum is an integer
+    below 2^24 and the sum is exact in any order, as for `data` above (whose
+    [0, 15] would pass 2^24 at these counts)."""
+    import torch
+
+    H.init(0)  # num_cus() is 0 before the device is opened
+    st = H.num_cus() * 256
+    assert st > 0
+    nmax = max(_unroll_counts(st, 4, 8)[-1], _unroll_counts(st, 2, 8)[-1]) + 8
+    hi = min(15, ((1 << 24) - 1) // nmax)
+    assert hi >= 1
+    base = np.random.default_rng(13).integers(0, hi + 1, size=nmax)
+    prefix = np.concatenate(([0], np.cumsum(base, dtype=np.int64)))
+    dev = {dt: torch.from_numpy(base.astype(dt)).cuda() for dt in UNROLL_DTYPES}
+    const = {dt: torch.full((nmax,), MAX_CONST, dtype=getattr(torch, dt), device="cuda") for dt in UNROLL_DTYPES}
+    return {"st": st, "base": base, "prefix": prefix, "dev": dev, "const": const}
+
+
+def _reduce_dev(torch, a, dev, offset, n, mode):
+    """One reducing sweep of dev[offset : offset + n] into the reset atomic a."""
+    stream = torch.cuda.current_stream().cuda_stream
+    a.reset(stream)
+    assert dev.data_ptr() % 16 == 0
+    H.forasync_reduce(a, dev.data_ptr() + offset * dev.element_size(), [(0, n, 1, -1)], mode, stream)
+    return a.gather(stream)
+
+
+@pytest.mark.parametrize("unroll", UNROLLS)
+@pytest.mark.parametrize("dt", UNROLL_DTYPES)
+def test_forasync_reduce_unrolled_sum_at_loop_bounds(big, dt, unroll, monkeypatch):
+    import torch
+
+    monkeypatch.setenv("HCLIB_HIP_REDUCE_BLOCKS_PER_CU", "1")
+    monkeypatch.setenv("HCLIB_HIP_REDUCE_UNROLL", str(unroll))
+    with H.Atomic(dt, "sum", 0) as a:
+        for n in _unroll_counts(big["st"], _vec(dt), unroll):
+            for offset, mode in ((0, H.FORASYNC_MODE_FLAT), (1, H.FORASYNC_MODE_RECURSIVE)):
+                val = _reduce_dev(torch, a, big["dev"][dt], offset, n, mode)
+                want = int(big["prefix"][offset + n] - big["prefix"][offset])
+                assert want == int(big["base"][offset:offset + n].sum()) < 1 << 24
+                assert val == want, (dt, unroll, n, offset)
+
+
+def _max_positions(st, N, U, n, head):
+    """Element indices that each lie in a different region of k_reduce_contig's
+    sweep of n elements after `head` head elements, on a grid of st lanes."""
+    nv = (n - head) // N
+    assert nv >= st and (n - head) % N == N - 1  # the full grid; a tail of N - 1
+    gt = np.arange(st, dtype=np.int64)
+    # lane gt leaves the unrolled loop at vector out[gt] = gt + k U st, after k rounds
+    k = np.maximum(nv - (U - 1) * st - gt + U * st - 1, 0) // (U * st)
+    out = gt + k * U * st
+    pos = {
+        "first element": 0,
+        "last element": n - 1,
+        "first vector": head,
+        "last vector": head + (nv - 1) * N + N - 1,
+        "last vector of the unrolled loop": head + int((out - st)[k > 0].max()) * N + 1,
+    }
+    if head:
+        pos["last head element"] = head - 1
+    rem = out[out < nv]
+    assert (rem.size == 0) == (U == 1)  # U = 1 has no remainder loop to enter
+    if rem.size:
+        pos["first vector of the remainder loop"] = head + int(rem.min()) * N
+        pos["last vector of the remainder loop"] = head + int((gt + (nv - 1 - gt) // st * st)[out < nv].max()) * N + N - 1
+    assert all(0 <= p < n for p in pos.values())
+    return pos
+
+
+@pytest.mark.parametrize("unroll", UNROLLS)
+@pytest.mark.parametrize("dt", UNROLL_DTYPES)
+def test_forasync_reduce_unrolled_max_sees_every_region(big, dt, unroll, monkeypatch):
+    """A constant array with one larger element, one launch per position."""
+    import torch
+
+    monkeypatch.setenv("HCLIB_HIP_REDUCE_BLOCKS_PER_CU", "1")
+    monkeypatch.setenv("HCLIB_HIP_REDUCE_UNROLL", str(unroll))
+    N, st, x = _vec(dt), big["st"], big["const"][dt]
+    with H.Atomic(dt, "max", _lowest(dt)) as a:
+        for offset in (0, 1):
+            head = (N - offset) % N
+            n = _unroll_counts(st, N, unroll)[-1]
+            n += (N - 1 - (n - head)) % N  # a tail of N - 1 elements behind the last vector
+            assert _reduce_dev(torch, a, x, offset, n, H.FORASYNC_MODE_FLAT) == MAX_CONST
+            for name, p in _max_positions(st, N, unroll, n, head).items():
+                x[offset + p] = MAX_PEAK
+                val = _reduce_dev(torch, a, x, offset, n, H.FORASYNC_MODE_RECURSIVE)
+                x[offset + p] = MAX_CONST
+                assert val == MAX_PEAK, (dt, unroll, offset, name, p)
+            # one element before and one past the range are not read
+            x[offset + n] = MAX_PEAK
+            if offset:
+                x[offset - 1] = MAX_PEAK
+            val = _reduce_dev(torch, a, x, offset, n, H.FORASYNC_MODE_FLAT)
+            x[offset + n] = MAX_CONST
+            x[:offset] = MAX_CONST
+            assert val == MAX_CONST, (dt, unroll, offset, "outside the range")
