@@ -116,6 +116,15 @@ class NQueensResult(C.Structure):
                 ("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
 
 
+class StrassenResult(C.Structure):
+    """hclib_hip_strassen_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("splits", C.c_uint64), ("base", C.c_uint64), ("tiles", C.c_uint64),
+                ("pre_bands", C.c_uint64), ("combine_bands", C.c_uint64), ("finishes", C.c_uint64),
+                ("check_ins", C.c_uint64), ("workspace_bytes", C.c_uint64),
+                ("kernel_ms", C.c_double), ("gflops", C.c_double)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -137,6 +146,7 @@ EXPORTS_HIP = [
     "hclib_hip_forasync_reduce", "hclib_hip_cholesky", "hclib_hip_sort_i64", "hclib_hip_sort_bounds",
     "hclib_hip_sparselu_genmat", "hclib_hip_sparselu_plan", "hclib_hip_sparselu", "hclib_hip_sparselu_bmod_rate",
     "hclib_hip_nqueens", "hclib_hip_nqueens_bounds",
+    "hclib_hip_strassen", "hclib_hip_strassen_bounds", "hclib_hip_strassen_last_ticks",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -214,6 +224,11 @@ def lib():
                                                    C.POINTER(C.c_double)]
         L.hclib_hip_nqueens.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(NQueensResult), C.POINTER(C.c_uint64)]
         L.hclib_hip_nqueens_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_strassen.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                         C.POINTER(StrassenResult)]
+        L.hclib_hip_strassen_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_strassen_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_strassen_last_ticks.restype = None
         _lib = L
     return _lib
 
@@ -736,6 +751,60 @@ def nqueens_bounds(n: int, form: str = "bots", task_depth: int = 0) -> dict:
     out = (C.c_uint64 * 2)()
     _check(lib().hclib_hip_nqueens_bounds(n, _nqueens_form(form), task_depth, out), "hclib_hip_nqueens_bounds")
     return {"tasks": out[0], "scopes": out[1]}
+
+
+# ------------------------------------------------------------ BOTS Strassen
+def strassen(a, b, cutoff: int = 0, band_rows: int = 0):
+    """BOTS Strassen on dynamic device dataflow (hclib_hip_strassen): a and b
+    are square float64 arrays of one power-of-two size; returns (a x b as the
+    reference's OptimizedStrassenMultiply computes it, bit for bit, stats).
+    cutoff is the reference's (0 = 64), band_rows the rows per band task of the
+    two sweeps (0 = the default: 8, or 16 for a tree of 8192 leaf multiplies or
+    more)."""
+    import numpy as np
+
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    b = np.ascontiguousarray(b, dtype=np.float64)
+    if a.ndim != 2 or a.shape[0] != a.shape[1] or b.shape != a.shape:
+        raise ValueError("strassen: a and b must be square matrices of the same size")
+    c = np.empty_like(a)
+    r = StrassenResult()
+    _check(lib().hclib_hip_strassen(a.ctypes.data, b.ctypes.data, c.ctypes.data, a.shape[0], cutoff, band_rows,
+                                    C.byref(r)), "hclib_hip_strassen")
+    return c, {k: getattr(r, k) for k, _ in StrassenResult._fields_}
+
+
+def strassen_bounds(n: int, cutoff: int = 0, band_rows: int = 0) -> dict:
+    """What a strassen() of size n allocates (hclib_hip_strassen_bounds), exact
+    and on the host alone: device tasks, finish scopes, wait nodes and the
+    bytes of the temporaries."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().hclib_hip_strassen_bounds(n, cutoff, band_rows, out), "hclib_hip_strassen_bounds")
+    return {"tasks": out[0], "scopes": out[1], "wait_nodes": out[2], "workspace_bytes": out[3]}
+
+
+def strassen_waves_per_cu(n: int, cutoff: int = 0) -> int:
+    """The persistent waves per CU a strassen() of this tree launches (the rule
+    of hclib_amd/csrc/strassen.hip, str_waves_per_cu, restated: measurements
+    divide the last launch's ticks by them): 8 from 8192 leaf multiplies on, 2
+    from 1024 on, else 1; HCLIB_HIP_STRASSEN_WAVES_PER_CU overrides it."""
+    env = os.environ.get("HCLIB_HIP_STRASSEN_WAVES_PER_CU")
+    if env:
+        return min(max(int(env), 1), 8)
+    cutoff = cutoff or 64
+    calls, size = 1, n
+    while size > cutoff:
+        calls, size = calls * 7, size // 2
+    leaves = calls * (size // 64) ** 2 if size > 64 else calls
+    return 8 if leaves >= 8192 else (2 if leaves >= 1024 else 1)
+
+
+def strassen_last_ticks() -> dict:
+    """Wave time of the last strassen() by task class, in ticks of the 100 MHz
+    device clock (hclib_hip_strassen_last_ticks)."""
+    out = (C.c_uint64 * 6)()
+    lib().hclib_hip_strassen_last_ticks(out)
+    return dict(zip(("multiply", "pre", "combine", "split", "fork", "post"), out))
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

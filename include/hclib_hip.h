@@ -47,6 +47,11 @@
  *                                    125-182), and the flat form's asyncs and counter
  *                                    (full-apps/nqueens.cpp:41-60), as task kinds of
  *                                    the work-stealing megakernel
+ *   hclib_hip_strassen               the seven asyncs, their finish scopes and the
+ *                                    taskwait of BOTS strassen (bots/strassen/
+ *                                    strassen.c, strassen.ref.c:580-788), the two
+ *                                    sweeps as band tasks, as one launch of dynamic
+ *                                    device dataflow
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -701,6 +706,57 @@ typedef struct {
 int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nqueens_result_t *result,
                       uint64_t *hist /* n + 1 entries, may be NULL */);
 int hclib_hip_nqueens_bounds(int n, int form, int task_depth, uint64_t out[2]);
+
+/* ------------------------------------------------------------ Strassen */
+/* BOTS Strassen (test/performance-regression/full-apps/bots/strassen:
+ * strassen.ref.c the algorithm, strassen.c the HClib port) as ONE launch of
+ * dynamic device dataflow: C = A x B by OptimizedStrassenMultiply(C, A, B, n,
+ * n, n, n), every call of its tree a device task, the port's finish scopes as
+ * dyn_finish_*, the two sweeps of a call split into bands of band_rows rows
+ * that check in to a scope dynamically (hclib_amd/csrc/strassen.hip has the
+ * task graph). a, b, c are host arrays of n x n doubles, row-major and dense.
+ * cutoff is the reference's (a product of at most cutoff rows is multiplied
+ * directly); 0 selects its default, 64. band_rows 0 selects 8, or 16 where
+ * the tree has 8192 or more leaf multiplies (bases, or the 64 x 64 tiles of
+ * larger bases): n >= 2048 at the default cutoff.
+ * The result is bit-identical to OptimizedStrassenMultiply_seq compiled
+ * without fused multiply-add: the reference's operation order in both sweeps,
+ * and in a base product, for every element, the chain over ascending k that
+ * starts from the first product (not from 0.0), each product and each sum
+ * rounded on its own. (The reference's driver passes its matrices in another
+ * order than strassen_main_par declares them and checks two matrices nobody
+ * wrote; the target here is the multiply itself)
+ * HCLIB_HIP_EINVAL before the device is touched: a, b or c NULL, n not a
+ * power of two, n < 16, n > 16384, cutoff in 1 .. 15 (or negative: the
+ * reference's naive kernels step 8 columns on a quadrant of 8 x 8 at the
+ * least), band_rows < 0, and a call tree whose arena (3 n^2 doubles and the
+ * temporaries) reaches 2^32 doubles, which the tasks' 32-bit element offsets
+ * cannot address. An arena the device cannot hold is HCLIB_HIP_ENOMEM.
+ * tasks .. check_ins are what the device ran and equal the bounds; base counts
+ * the products of at most cutoff rows, tiles the 64 x 64 tile tasks of bases
+ * larger than 64. workspace_bytes is the temporaries: eleven quadrants per
+ * splitting call, all calls live at once (258 MB at n = 1024 / cutoff 64); the
+ * three matrices sit in front of them. Both copies are outside kernel_ms.
+ * hclib_hip_strassen_bounds: host only, no GPU: out[0] tasks, out[1] finish
+ * scopes (promises), out[2] wait nodes, out[3] workspace bytes, all exact (the
+ * tree does not depend on the data); the launch allocates exactly these. The
+ * same argument checks, but for the matrices.
+ * hclib_hip_strassen_last_ticks: where the last launch's wave time went, ticks
+ * of the 100 MHz device clock summed over the tasks of each class, each from
+ * the start of its body to the end of its check-out: [0] base and tile
+ * multiplies, [1] PRE bands, [2] COMBINE bands, [3] MUL splits, [4] FORK,
+ * [5] POST. */
+typedef struct {
+    uint64_t tasks, splits, base, tiles, pre_bands, combine_bands;
+    uint64_t finishes, check_ins;
+    uint64_t workspace_bytes;
+    double kernel_ms;     /* device events around the one launch */
+    double gflops;        /* 2 n^3 / kernel time: the classical count, not what Strassen executes */
+} hclib_hip_strassen_result_t;
+int hclib_hip_strassen(const double *a, const double *b, double *c, int n,
+                       int cutoff, int band_rows, hclib_hip_strassen_result_t *result);
+int hclib_hip_strassen_bounds(int n, int cutoff, int band_rows, uint64_t out[4]);
+void hclib_hip_strassen_last_ticks(uint64_t out[6]);
 
 #ifdef __cplusplus
 }
