@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 # HCLIB_AMD_LIB selects a diagnostic variant (python -m hclib_amd.build --variant X)
@@ -134,7 +134,8 @@ class AtomicViewStruct(C.Structure):
 
 # every symbol include/hclib_hip.h and include/hclib.h declare (checked by tests)
 EXPORTS_HIP = [
-    "hclib_hip_init", "hclib_hip_finalize", "hclib_hip_last_error", "hclib_hip_num_cus",
+    "hclib_hip_init", "hclib_hip_finalize", "hclib_hip_device_memory_live", "hclib_hip_last_error",
+    "hclib_hip_num_cus",
     "hclib_hip_version", "hclib_hip_forasync", "hclib_hip_forasync_triad_f32",
     "hclib_hip_num_workers", "hclib_hip_uts_search", "hclib_hip_uts_num_children_host",
     "hclib_hip_uts_bucket_check", "hclib_hip_sha1_calibrate",
@@ -166,6 +167,9 @@ def lib():
         L = C.CDLL(LIB_PATH)
         L.hclib_hip_version.restype = C.c_char_p
         L.hclib_hip_last_error.restype = C.c_char_p
+        L.hclib_hip_finalize.restype = None
+        L.hclib_hip_device_memory_live.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_device_memory_live.restype = None
         L.hclib_hip_forasync_triad_f32.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_float,
                                                    C.c_int64, C.c_void_p]
         L.hclib_hip_forasync.argtypes = [C.c_int, C.c_void_p, C.c_int, C.POINTER(LoopDomain),
@@ -245,6 +249,18 @@ def version() -> str:
 
 def init(device: int = 0) -> None:
     _check(lib().hclib_hip_init(device), "hclib_hip_init")
+
+
+def finalize() -> None:
+    """Free every device allocation the library holds on its own account; `init` starts again."""
+    lib().hclib_hip_finalize()
+
+
+def device_memory_live() -> Tuple[int, int]:
+    """(live device allocations, their bytes) of the library's own account: arenas and per-call buffers."""
+    out = (C.c_uint64 * 2)()
+    lib().hclib_hip_device_memory_live(out)
+    return int(out[0]), int(out[1])
 
 
 def num_cus() -> int:

@@ -120,23 +120,22 @@ extern "C" int hclib_hip_sha1_calibrate(int chains, int waves_per_cu, int iters,
     }
     HX_TRY(ensure_device());
     Module &m = mod();
-    void *d = nullptr;
-    HX_HIP(hipMalloc(&d, 4096 + 256));
-    uint32_t *seed = (uint32_t *)d, *sink = (uint32_t *)((char *)d + 4096);
-    int rc = hip_check(hipMemsetAsync(d, 0x5a, 4096 + 256, m.stream), "memset");
+    DevBuf buf;
+    HX_TRY(buf.alloc(4096 + 256, "hclib_hip_sha1_calibrate"));
+    char *d = buf.p;
+    uint32_t *seed = (uint32_t *)d, *sink = (uint32_t *)(d + 4096);
+    HX_HIP(hipMemsetAsync(d, 0x5a, 4096 + 256, m.stream));
     const int blocks = m.num_cus * waves_per_cu;
-    for (int rep = 0; rep < 2 && rc == HCLIB_HIP_OK; ++rep) {  // warm-up, then the timed launch
-        if (rep == 1) rc = hip_check(hipEventRecord(m.ev0, m.stream), "event");
+    for (int rep = 0; rep < 2; ++rep) {  // warm-up, then the timed launch
+        if (rep == 1) HX_HIP(hipEventRecord(m.ev0, m.stream));
         if (chains == 1) hipLaunchKernelGGL(k_sha1_chain<1>, dim3(blocks), dim3(64), 0, m.stream, seed, iters, sink);
         else hipLaunchKernelGGL(k_sha1_chain<2>, dim3(blocks), dim3(64), 0, m.stream, seed, iters, sink);
-        if (rc == HCLIB_HIP_OK) rc = hip_check(hipGetLastError(), "sha1 calibration launch");
+        HX_HIP(hipGetLastError());
     }
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipEventRecord(m.ev1, m.stream), "event");
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipStreamSynchronize(m.stream), "sync");
+    HX_HIP(hipEventRecord(m.ev1, m.stream));
+    HX_HIP(hipStreamSynchronize(m.stream));
     float ms = 0;
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipEventElapsedTime(&ms, m.ev0, m.ev1), "elapsed");
-    (void)hipFree(d);
-    if (rc != HCLIB_HIP_OK) return rc;
+    HX_HIP(hipEventElapsedTime(&ms, m.ev0, m.ev1));
     *sha1_per_s = ms > 0 ? (double)blocks * 64.0 * chains * iters / (ms * 1e-3) : 0.0;
     if (kernel_ms) *kernel_ms = ms;
     return HCLIB_HIP_OK;
@@ -151,14 +150,15 @@ extern "C" int hclib_hip_atomic_calibrate(int mode, int iters, double *mops_per_
     HX_TRY(ensure_device());
     Module &m = mod();
     const size_t table = 256ull << 20;  // 16-B records spread past the Infinity Cache's reach
-    void *d = nullptr;
-    HX_HIP(hipMalloc(&d, table + 256));
-    unsigned long long *sink = (unsigned long long *)((char *)d + table);
-    int rc = hip_check(hipMemsetAsync(d, 0, table + 256, m.stream), "memset");
+    DevBuf buf;
+    HX_TRY(buf.alloc(table + 256, "hclib_hip_atomic_calibrate"));
+    char *d = buf.p;
+    unsigned long long *sink = (unsigned long long *)(d + table);
+    HX_HIP(hipMemsetAsync(d, 0, table + 256, m.stream));
     double ops = 0;
     // warm-up launch (page tables, clocks), then the timed one
-    for (int rep = 0; rep < 2 && rc == HCLIB_HIP_OK; ++rep) {
-        if (rep == 1) rc = hip_check(hipEventRecord(m.ev0, m.stream), "event");
+    for (int rep = 0; rep < 2; ++rep) {
+        if (rep == 1) HX_HIP(hipEventRecord(m.ev0, m.stream));
         const int blocks = m.num_cus * 8;
         if (mode == 0) {  // 32 waves per CU, every lane its own record
             hipLaunchKernelGGL(k_atomic_scatter_ret64, dim3(blocks), dim3(256), 0, m.stream,
@@ -173,14 +173,12 @@ extern "C" int hclib_hip_atomic_calibrate(int mode, int iters, double *mops_per_
                                (uint32_t)((64ull << 20) / 256 - 1), iters);
             ops = (double)blocks * 256 * iters;
         }
-        if (rc == HCLIB_HIP_OK) rc = hip_check(hipGetLastError(), "atomic calibration launch");
+        HX_HIP(hipGetLastError());
     }
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipEventRecord(m.ev1, m.stream), "event");
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipStreamSynchronize(m.stream), "sync");
+    HX_HIP(hipEventRecord(m.ev1, m.stream));
+    HX_HIP(hipStreamSynchronize(m.stream));
     float ms = 0;
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipEventElapsedTime(&ms, m.ev0, m.ev1), "elapsed");
-    (void)hipFree(d);
-    if (rc != HCLIB_HIP_OK) return rc;
+    HX_HIP(hipEventElapsedTime(&ms, m.ev0, m.ev1));
     *mops_per_s = ms > 0 ? ops / (ms * 1e3) : 0.0;
     if (kernel_ms) *kernel_ms = ms;
     return HCLIB_HIP_OK;

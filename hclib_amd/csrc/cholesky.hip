@@ -37,8 +37,7 @@
 
 #include <vector>
 
-#include "hx_module.h"
-#include "../../include/hclib_hip/hx_dag.h"
+#include "hx_client.h"
 
 namespace hx {
 namespace {
@@ -233,13 +232,8 @@ __device__ void chol_panel(const CholCtx &c, double *A, double *Li, int T, int c
     }
 }
 
-struct CholKind {
-    using Ctx = CholCtx;
+struct CholKind : OnePromiseKind<CholCtx> {
     static constexpr bool kSc1Payload = true;  // tiles move by ld_agent / st_agent only (ldt / stt)
-    // one promise per task, the tile version it makes: run_dag_group's split put
-    static constexpr int kPutN = 1;
-    __device__ static void promises(const Ctx &, uint32_t t, uint32_t (&p)[1]) { p[0] = t; }
-    __device__ static void datums(const Ctx &, uint32_t, unsigned long long (&d)[1]) { d[0] = 0ull; }
     __device__ static bool run_group(const Ctx &c, uint32_t, const uint32_t *pl, int) {
         const uint32_t kind = pl[0], k = pl[1], j = pl[2], i = pl[3];
         const int T = c.T;
@@ -261,12 +255,6 @@ struct CholKind {
 __global__ __launch_bounds__(kCholThreads) void k_cholesky(CholCtx c, DagView v) {
     run_dag_group<CholKind>(c, v, nullptr);
 }
-
-struct CholState {
-    void *buf = nullptr;
-    size_t bytes = 0;
-};
-CholState g_chol;
 
 }  // namespace
 }  // namespace hx
@@ -307,32 +295,18 @@ extern "C" int hclib_hip_cholesky(const double *a, int n, int tile, int mode, do
     HX_TRY(ensure_device());
     Module &m = mod();
 
-    // the graph, in the reference's program order (cholesky.cpp:80-124):
-    // `last` is the task that made each tile's newest version (none: version 0)
-    const uint32_t none = 0xffffffffu;
+    // the graph, in the reference's program order (cholesky.cpp:80-124)
     const size_t T2 = (size_t)tile * tile, ntiles = (size_t)(nt * (nt + 1) / 2);
     auto tidx = [](uint64_t j, uint64_t i) { return (size_t)(j * (j + 1) / 2 + i); };
-    std::vector<uint32_t> last(ntiles, none), payload, off, ids;
-    payload.reserve(ntasks * 4);
-    off.reserve(ntasks + 1);
-    ids.reserve(ntasks * 3);
-    off.push_back(0);
-    auto task = [&](uint32_t kind, uint64_t k, uint64_t j, uint64_t i, std::initializer_list<size_t> in, size_t outp) {
-        const uint32_t id = (uint32_t)(off.size() - 1);
-        const uint32_t pl[4] = {kind, (uint32_t)k, (uint32_t)j, (uint32_t)i};
-        payload.insert(payload.end(), pl, pl + 4);
-        for (size_t t : in)
-            if (last[t] != none) ids.push_back(last[t]);
-        off.push_back((uint32_t)ids.size());
-        last[outp] = id;
-    };
-    for (uint64_t k = 0; k < nt; ++k) {
-        task(kCholPotrf, k, k, k, {tidx(k, k)}, tidx(k, k));
-        for (uint64_t j = k + 1; j < nt; ++j) task(kCholTrsm, k, j, k, {tidx(j, k), tidx(k, k)}, tidx(j, k));
-        for (uint64_t j = k + 1; j < nt; ++j) {
-            for (uint64_t i = k + 1; i < j; ++i)
-                task(kCholGemm, k, j, i, {tidx(j, i), tidx(i, k), tidx(j, k)}, tidx(j, i));
-            task(kCholSyrk, k, j, j, {tidx(j, j), tidx(j, k)}, tidx(j, j));
+    VersionGraph g(ntiles);
+    g.reserve(ntasks, 3);
+    for (uint32_t k = 0; k < nt; ++k) {
+        g.task(kCholPotrf, k, k, k, tidx(k, k), {tidx(k, k)});
+        for (uint32_t j = k + 1; j < nt; ++j) g.task(kCholTrsm, k, j, k, tidx(j, k), {tidx(j, k), tidx(k, k)});
+        for (uint32_t j = k + 1; j < nt; ++j) {
+            for (uint32_t i = k + 1; i < j; ++i)
+                g.task(kCholGemm, k, j, i, tidx(j, i), {tidx(j, i), tidx(i, k), tidx(j, k)});
+            g.task(kCholSyrk, k, j, j, tidx(j, j), {tidx(j, j), tidx(j, k)});
         }
     }
 
@@ -352,42 +326,26 @@ extern "C" int hclib_hip_cholesky(const double *a, int n, int tile, int mode, do
             }
         }
     const size_t bytes = ndoubles * sizeof(double);
-    if (bytes > g_chol.bytes) {
-        if (g_chol.buf) (void)hipFree(g_chol.buf);
-        g_chol.buf = nullptr;
-        g_chol.bytes = 0;
-        if (hipMalloc(&g_chol.buf, bytes) != hipSuccess) {
-            set_error("hclib_hip_cholesky: hipMalloc(%zu) failed", bytes);
-            return HCLIB_HIP_ENOMEM;
-        }
-        g_chol.bytes = bytes;
-    }
-    // (`h` outlives the copy: the stream is synchronised before it goes)
-    HX_HIP(hipMemcpyAsync(g_chol.buf, h.data(), bytes, hipMemcpyHostToDevice, m.stream));
+    double *buf = nullptr;
+    HX_TRY(arena_reserve(kArenaCholesky, bytes, "hclib_hip_cholesky", (void **)&buf));
+    // (`h` outlives the copy: launch_dag_group synchronises the stream)
+    HX_HIP(hipMemcpyAsync(buf, h.data(), bytes, hipMemcpyHostToDevice, m.stream));
 
     CholCtx c;
-    c.tiles = (double *)g_chol.buf + hdr;
-    c.fail = (int *)g_chol.buf;
+    c.tiles = buf + hdr;
+    c.fail = (int *)buf;
     c.err = nullptr;
     c.T = tile;
     // one persistent workgroup per CU: the sc1 hand-off's measured form
     const int wgs = 1;
-    hclib_hip_dag_launch_t L;
-    int rc = hclib_hip_dag_begin((uint32_t)ntasks, (uint32_t)ntasks, 4, payload.data(), off.data(), ids.data(),
-                                 nullptr, nullptr, wgs, 0, &L);
-    if (rc) {
-        (void)hipStreamSynchronize(m.stream);
-        return rc;
-    }
-    const DagView &v = *(const DagView *)L.view;
-    c.err = v.err;
-    rc = check_resident((const void *)k_cholesky, L.grid, kCholThreads, 0, "hclib_hip_cholesky");
-    if (rc == HCLIB_HIP_OK) hipLaunchKernelGGL(k_cholesky, dim3(L.grid), dim3(kCholThreads), 0, m.stream, c, v);
     hclib_hip_dag_stats_t st{};
-    const int rc_end = hclib_hip_dag_end("hclib_hip_cholesky", nullptr, nullptr, &st);
-    if (rc) return rc;  // nothing was launched; dag_end closed the launch
+    const int rc = launch_dag_group(g, wgs, (const void *)k_cholesky, kCholThreads, "hclib_hip_cholesky", &st,
+                                    [&](int grid, const DagView &v) {
+                                        c.err = v.err;
+                                        hipLaunchKernelGGL(k_cholesky, dim3(grid), dim3(kCholThreads), 0, m.stream, c, v);
+                                    });
     int fail_col = -1;
-    if (rc_end == HCLIB_HIP_EDEVICE) (void)hipMemcpy(&fail_col, c.fail, sizeof(int), hipMemcpyDeviceToHost);
+    if (rc == HCLIB_HIP_EDEVICE) (void)hipMemcpy(&fail_col, c.fail, sizeof(int), hipMemcpyDeviceToHost);
     if (result) {
         result->tasks = st.tasks;
         result->puts = st.puts;
@@ -405,8 +363,8 @@ extern "C" int hclib_hip_cholesky(const double *a, int n, int tile, int mode, do
                   fail_col);
         return HCLIB_HIP_EDEVICE;
     }
-    if (rc_end) return rc_end;
-    HX_HIP(hipMemcpy(h.data(), g_chol.buf, bytes, hipMemcpyDeviceToHost));
+    if (rc) return rc;
+    HX_HIP(hipMemcpy(h.data(), buf, bytes, hipMemcpyDeviceToHost));
     // the factor's lower triangle; the strict upper triangle as +0.0
     for (uint64_t j = 0; j < nt; ++j)
         for (int r = 0; r < tile; ++r) {

@@ -21,10 +21,7 @@ namespace {
 struct DagState {
     bool active = false;
     DagView view{};
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
     uint32_t ntasks = 0, npromises = 0;
-    unsigned long long *trace = nullptr;  // HX_DAG_TRACE builds: the per-task timeline
 };
 
 DagState g_dag;
@@ -116,17 +113,8 @@ extern "C" int hclib_hip_dag_begin(uint32_t ntasks, uint32_t npromises, uint32_t
     memcpy(&h[o_sat], sat.data(), sat.size() * 4);
     if (ntasks && payload_words) memcpy(&h[o_pay], payload, (size_t)ntasks * payload_words * 4);
     memcpy(&h[o_ready], ready.data(), ready.size() * 4);
-    if (bytes > g_dag.arena_bytes) {
-        if (g_dag.arena) (void)hipFree(g_dag.arena);
-        g_dag.arena = nullptr;
-        g_dag.arena_bytes = 0;
-        if (hipMalloc(&g_dag.arena, bytes) != hipSuccess) {
-            set_error("hclib_hip_dag_begin: hipMalloc(%zu) failed", bytes);
-            return HCLIB_HIP_ENOMEM;
-        }
-        g_dag.arena_bytes = bytes;
-    }
-    char *d = (char *)g_dag.arena;
+    char *d = nullptr;
+    HX_TRY(arena_reserve(kArenaDag, bytes, "hclib_hip_dag_begin", (void **)&d));
     HX_TRY(upload_async(d, h.data(), bytes, m.stream));
     DagView &v = g_dag.view;
     v.head = (uint32_t *)(d + o_ctl);
@@ -149,12 +137,11 @@ extern "C" int hclib_hip_dag_begin(uint32_t ntasks, uint32_t npromises, uint32_t
     // diagnostic: per-task timeline (hx_dag.h kDagTraceWords), written to the
     // file HCLIB_HIP_DAG_TRACE names at hclib_hip_dag_end
     if (getenv("HCLIB_HIP_DAG_TRACE") && ntasks) {
-        if (g_dag.trace) (void)hipFree(g_dag.trace);
-        g_dag.trace = nullptr;
         const size_t tb = (size_t)ntasks * kDagTraceWords * 8;
-        if (hipMalloc((void **)&g_dag.trace, tb) == hipSuccess) {
-            HX_HIP(hipMemsetAsync(g_dag.trace, 0, tb, m.stream));
-            v.trace = g_dag.trace;
+        unsigned long long *trace = nullptr;
+        if (arena_reserve(kArenaDagTrace, tb, "hclib_hip_dag_begin", (void **)&trace) == HCLIB_HIP_OK) {
+            HX_HIP(hipMemsetAsync(trace, 0, tb, m.stream));
+            v.trace = trace;
         }
     }
 #endif
@@ -265,8 +252,6 @@ namespace {
 struct DynState {
     bool active = false;
     DynView view{};
-    void *arena = nullptr;
-    size_t arena_bytes = 0;
     unsigned long long finish[2] = {0, 0};  // the last launch's scopes opened, tasks checked in
 };
 DynState g_dyn;
@@ -300,17 +285,8 @@ extern "C" int hclib_hip_dyn_begin(uint32_t payload_words, const uint32_t *root_
     const size_t o_tpay = o_tdeps + up256((size_t)task_cap * 4);
     const size_t o_ready = o_tpay + up256((size_t)task_cap * payload_words * 4 + 4);
     const size_t bytes = o_ready + up256((size_t)rcap * 4);
-    if (bytes > g_dyn.arena_bytes) {
-        if (g_dyn.arena) (void)hipFree(g_dyn.arena);
-        g_dyn.arena = nullptr;
-        g_dyn.arena_bytes = 0;
-        if (hipMalloc(&g_dyn.arena, bytes) != hipSuccess) {
-            set_error("hclib_hip_dyn_begin: hipMalloc(%zu) failed", bytes);
-            return HCLIB_HIP_ENOMEM;
-        }
-        g_dyn.arena_bytes = bytes;
-    }
-    char *d = (char *)g_dyn.arena;
+    char *d = nullptr;
+    HX_TRY(arena_reserve(kArenaDyn, bytes, "hclib_hip_dyn_begin", (void **)&d));
     // control + stats zeroed, heads and ready slots 0xff, then the roots
     HX_HIP(hipMemsetAsync(d, 0, o_datum, m.stream));
     HX_HIP(hipMemsetAsync(d + o_phead, 0xff, (size_t)pcap * 4, m.stream));
@@ -405,7 +381,8 @@ extern "C" void hclib_hip_dyn_finish_stats(uint64_t out[2]) {
 
 extern "C" int hclib_hip_dyn_datum(uint32_t first, uint32_t n, uint64_t *datum, uint8_t *put) {
     const DynView &v = g_dyn.view;
-    if (g_dyn.active || !g_dyn.arena || (uint64_t)first + n > v.pcap) {
+    // (the view is of the last launch's pools while the arena they lie in lives)
+    if (g_dyn.active || !mod().arenas[kArenaDyn].mem || (uint64_t)first + n > v.pcap) {
         set_error("hclib_hip_dyn_datum: no finished launch or promises [%u, %u) outside the pool", first, first + n);
         return HCLIB_HIP_EINVAL;
     }

@@ -288,15 +288,16 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
     // (2 items per worker, at most kFibSeedCap: fib(30) 0.70-0.74 -> 0.47-0.49 ms,
     // profiles/r04/fibseed_sweep.log, fibseed2_sweep.log; 0: from one root)
     const size_t sb = seed_pw > 0 ? (64 + 2 * (size_t)kFibSeedCap) * 4 : 0;
-    void *dmem = nullptr;
-    HX_HIP(hipMalloc(&dmem, jb + 512 + sb));
+    DevBuf buf;
+    HX_TRY(buf.alloc(jb + 512 + sb, "hclib_hip_fib"));
+    char *dmem = buf.p;
     FibCtx ctx;
     ctx.n = n;
     // LDS scopes (hx_finish.h LocalScopes, batched promotion): fib(30)
     // 0.807 -> 0.688 ms (profiles/r04/fiblds_sweep.log)
     ctx.local = env_int("HCLIB_HIP_FIB_LOCAL", 1);
     ctx.fin.scopes = (FinishScope *)dmem;
-    ctx.fin.next = (uint32_t *)((char *)dmem + ((jb + 255) & ~(size_t)255));
+    ctx.fin.next = (uint32_t *)(dmem + ((jb + 255) & ~(size_t)255));
     ctx.fin.cap = (uint32_t)ids;
     ctx.blocks = blocks;
     ctx.fin.root_value = (unsigned long long *)(ctx.fin.next + 16);
@@ -304,7 +305,7 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
     ctx.seed = nullptr;
     ctx.seed_per_wave = seed_pw;
     if (seed_pw > 0) {
-        ctx.seed = (uint32_t *)((char *)dmem + ((jb + 255) & ~(size_t)255) + 256);
+        ctx.seed = (uint32_t *)(dmem + ((jb + 255) & ~(size_t)255) + 256);
         HX_HIP(hipMemsetAsync(ctx.seed, 0, 256, m.stream));
     }
     PoolView pool;
@@ -331,10 +332,7 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
     // seeded: every wave starts holding its share (outstanding = every wave)
     HX_TRY(reset_sched(pool, ctx.seed ? (uint32_t)grid : 1u, false, (uint32_t)grid));
     HX_HIP(hipEventRecord(m.ev0, m.stream));
-    if (int rc0 = check_resident((const void *)k_fib, grid, 64, 0, "hclib_hip_fib")) {
-        (void)hipFree(dmem);
-        return rc0;
-    }
+    HX_TRY(check_resident((const void *)k_fib, grid, 64, 0, "hclib_hip_fib"));
     hipLaunchKernelGGL(k_fib, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
     HX_HIP(hipGetLastError());
     HX_HIP(hipEventRecord(m.ev1, m.stream));
@@ -349,7 +347,6 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
     }
     float ms = 0;
     (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    (void)hipFree(dmem);
     if (rc != HCLIB_HIP_OK) return rc;
     *value = (int64_t)v;
     if (result) {

@@ -12,6 +12,33 @@
 
 namespace hx {
 
+// Device memory the library holds on its own account has one owner, the
+// module: named grow-only arenas, which live from their first
+// use to hclib_hip_finalize, and per-call DevBufs. Both are counted
+// (hclib_hip_device_memory_live). Nothing here has a destructor that calls
+// HIP on the static module: HIP may be gone when statics are destroyed.
+enum ArenaId {
+    kArenaGlobals,     // SchedGlobals of the running launch
+    kArenaWaveStats,   // per-wave records of megakernel launches (WaveStat, hx_sched.h)
+    kArenaWaveCtr,     // per-worker exit records (hx_sched.h kWaveCtrWords), summed by finish_sched
+    kArenaTimeline,    // diagnostic worker timelines (HX_TIMELINE builds)
+    kArenaDeques,      // chunk deques, sized for the largest entry type (make_pool)
+    kArenaSeed,        // breadth-first seeding: two level buffers + control lines (reset_sched)
+    kArenaDag,         // hclib_hip_dag_begin's graph
+    kArenaDagTrace,    // HX_DAG_TRACE builds: the per-task timeline
+    kArenaDyn,         // hclib_hip_dyn_begin's pools
+    kArenaCholesky,    // tiles
+    kArenaSparselu,    // blocks and the slot table
+    kArenaSort,        // class counters, the array and tmp
+    kArenaStrassen,    // class counters, A, B, C and the temporaries
+    kArenaUtsTables,   // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
+    kArenaCount
+};
+struct Arena {
+    void *mem = nullptr;
+    size_t bytes = 0;
+};
+
 // Per-process module state (one bound device per process, like one rank
 // per GPU in the multi-GPU launch).
 struct Module {
@@ -21,9 +48,8 @@ struct Module {
     std::string arch;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    // chunk-deque arena, sized for the largest entry type, reused by launches
-    void *pool_mem = nullptr;
-    size_t pool_bytes = 0;
+    Arena arenas[kArenaCount];
+    bool uts_tables_cached = false;  // uts.hip's host tables match kArenaUtsTables (gone with it at finalize)
     SchedGlobals *globals = nullptr;
     unsigned long long last_counters[16] = {};  // counters of the last megakernel launch
     unsigned long long last_narrow[4] = {};     // SchedGlobals::narrow of the last launch
@@ -34,9 +60,6 @@ struct Module {
     std::vector<WaveStat> last_waves;  // the last launch's, copied back by finish_sched
     // per-worker exit records (hx_sched.h kWaveCtrWords), summed by finish_sched
     unsigned long long *wave_ctr = nullptr;
-    // breadth-first seeding arena (two level buffers + control lines)
-    void *seed_mem = nullptr;
-    size_t seed_bytes = 0;
     uint32_t rec_workers = 0;  // records the running launch writes
     // cross-GPU work sharing (hclib_hip_global_attach): the shared region's
     // view for sharded launches, hdr null while detached
@@ -58,6 +81,26 @@ int check_resident(const void *kern, int blocks, int threads, size_t lds, const 
 // host -> device copy of `bytes` at `src` in `stream` order through a pinned
 // staging buffer: `src` may be freed as soon as the call returns
 int upload_async(void *dst, const void *src, size_t bytes, hipStream_t stream);
+
+// At least `bytes` of arena `id` in *ptr. Grow-only: a larger request frees
+// and reallocates (contents are not kept; callers fill an arena per call), a
+// smaller one reuses. HCLIB_HIP_ENOMEM with "<who>: hipMalloc(<bytes>) failed".
+int arena_reserve(ArenaId id, size_t bytes, const char *who, void **ptr);
+
+// A per-call device buffer, freed on every return path. The module stream is
+// drained first: a kernel launched before an error return may still read it.
+class DevBuf {
+  public:
+    DevBuf() = default;
+    DevBuf(const DevBuf &) = delete;
+    DevBuf &operator=(const DevBuf &) = delete;
+    ~DevBuf();
+    int alloc(size_t bytes, const char *who);  // once; HCLIB_HIP_ENOMEM as arena_reserve
+    char *p = nullptr;
+
+  private:
+    size_t bytes_ = 0;
+};
 
 // Carve a PoolView for `words` u32 per entry out of the arena (grows it).
 int make_pool(uint32_t nq, uint32_t cap, uint32_t chunk, uint32_t words, PoolView *out);

@@ -21,6 +21,56 @@ void set_error(const char *fmt, ...) {
     va_end(ap);
 }
 
+// every device allocation the library holds on its own account goes through
+// these two: {live allocations, live bytes}
+static uint64_t g_live[2] = {0, 0};
+static bool dev_acquire(void **p, size_t bytes) {
+    if (hipMalloc(p, bytes) != hipSuccess) {
+        (void)hipGetLastError();  // an allocation that failed is reported, not left sticky
+        *p = nullptr;
+        return false;
+    }
+    g_live[0] += 1;
+    g_live[1] += bytes;
+    return true;
+}
+static void dev_release(void *p, size_t bytes) {
+    if (!p) return;
+    (void)hipFree(p);
+    g_live[0] -= 1;
+    g_live[1] -= bytes;
+}
+
+int arena_reserve(ArenaId id, size_t bytes, const char *who, void **ptr) {
+    Arena &a = g_mod.arenas[id];
+    if (bytes > a.bytes) {
+        dev_release(a.mem, a.bytes);
+        a = Arena();
+        if (!dev_acquire(&a.mem, bytes)) {
+            set_error("%s: hipMalloc(%zu) failed", who, bytes);
+            return HCLIB_HIP_ENOMEM;
+        }
+        a.bytes = bytes;
+    }
+    *ptr = a.mem;
+    return HCLIB_HIP_OK;
+}
+
+int DevBuf::alloc(size_t bytes, const char *who) {
+    if (!dev_acquire((void **)&p, bytes)) {
+        set_error("%s: hipMalloc(%zu) failed", who, bytes);
+        return HCLIB_HIP_ENOMEM;
+    }
+    bytes_ = bytes;
+    return HCLIB_HIP_OK;
+}
+
+DevBuf::~DevBuf() {
+    if (!p) return;
+    (void)hipStreamSynchronize(g_mod.stream);
+    dev_release(p, bytes_);
+}
+
 int check_resident(const void *kern, int blocks, int threads, size_t lds, const char *what) {
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, threads, lds) != hipSuccess) return HCLIB_HIP_OK;
@@ -72,18 +122,8 @@ int make_pool(uint32_t nq, uint32_t cap, uint32_t chunk, uint32_t words, PoolVie
     const size_t hdr = sizeof(QueueHdr) * nq;
     const size_t slots = (size_t)nq * cap;
     const size_t need = hdr + slots * 4 * 2 + slots * chunk * words * 4 + 4096;
-    Module &m = g_mod;
-    if (need > m.pool_bytes) {
-        if (m.pool_mem) (void)hipFree(m.pool_mem);
-        m.pool_mem = nullptr;
-        m.pool_bytes = 0;
-        if (hipMalloc(&m.pool_mem, need) != hipSuccess) {
-            set_error("hipMalloc(%zu) for the chunk deques failed", need);
-            return HCLIB_HIP_ENOMEM;
-        }
-        m.pool_bytes = need;
-    }
-    char *p = (char *)m.pool_mem;
+    char *p = nullptr;
+    HX_TRY(arena_reserve(kArenaDeques, need, "chunk deques", (void **)&p));
     out->hdr = (QueueHdr *)p;
     p += hdr;
     // {seq, cnt} pairs, 8-B aligned (hx_sched.h slot_ctl); cnt = seq + 1
@@ -171,16 +211,11 @@ int reset_sched(const PoolView &pool, uint32_t outstanding_init, bool global, ui
         const uint32_t cap = 8u * seed->target + 65536u;
         const size_t ctl = (size_t)kSeedCtlLines * 256;
         const size_t need = ctl + 2ull * cap * seed->words * 4;
-        if (need > m.seed_bytes) {
-            if (m.seed_mem) (void)hipFree(m.seed_mem);
-            m.seed_mem = nullptr;
-            m.seed_bytes = 0;
-            HX_HIP(hipMalloc(&m.seed_mem, need));
-            m.seed_bytes = need;
-        }
-        HX_HIP(hipMemsetAsync(m.seed_mem, 0, ctl, m.stream));
-        init.seed.ctl = (uint32_t *)m.seed_mem;
-        init.seed.buf = (uint32_t *)((char *)m.seed_mem + ctl);
+        char *seed_mem = nullptr;
+        HX_TRY(arena_reserve(kArenaSeed, need, "seeding", (void **)&seed_mem));
+        HX_HIP(hipMemsetAsync(seed_mem, 0, ctl, m.stream));
+        init.seed.ctl = (uint32_t *)seed_mem;
+        init.seed.buf = (uint32_t *)(seed_mem + ctl);
         init.seed.cap = cap;
         init.seed.target = seed->target;
         init.seed.max_levels = seed->max_levels;
@@ -192,12 +227,9 @@ int reset_sched(const PoolView &pool, uint32_t outstanding_init, bool global, ui
     // diagnostic timelines: only a HX_TIMELINE build writes them
     const int tl_cap = env_int("HCLIB_HIP_TIMELINE", 0);
     if (tl_cap > 0) {
-        if (!m.timeline || (uint32_t)tl_cap != m.timeline_cap) {
-            if (m.timeline) (void)hipFree(m.timeline);
-            m.timeline = nullptr;
-            HX_HIP(hipMalloc((void **)&m.timeline, (size_t)m.wave_stats_cap * tl_cap * 8));
-            m.timeline_cap = (uint32_t)tl_cap;
-        }
+        HX_TRY(arena_reserve(kArenaTimeline, (size_t)m.wave_stats_cap * tl_cap * 8, "worker timelines",
+                             (void **)&m.timeline));
+        m.timeline_cap = (uint32_t)tl_cap;
         HX_HIP(hipMemsetAsync(m.timeline, 0, (size_t)m.wave_stats_cap * tl_cap * 8, m.stream));
         init.timeline = m.timeline;
         init.timeline_cap = m.timeline_cap;
@@ -310,10 +342,11 @@ int hclib_hip_init(int device) {
     HX_HIP(hipStreamCreateWithFlags(&m.stream, hipStreamNonBlocking));
     HX_HIP(hipEventCreate(&m.ev0));
     HX_HIP(hipEventCreate(&m.ev1));
-    HX_HIP(hipMalloc((void **)&m.globals, sizeof(SchedGlobals)));
+    const char *who = "hclib_hip_init";
+    HX_TRY(arena_reserve(kArenaGlobals, sizeof(SchedGlobals), who, (void **)&m.globals));
     m.wave_stats_cap = (uint32_t)m.num_cus * 32;  // 32 waves per CU at most
-    HX_HIP(hipMalloc((void **)&m.wave_stats, sizeof(WaveStat) * m.wave_stats_cap));
-    HX_HIP(hipMalloc((void **)&m.wave_ctr, 8ull * kWaveCtrWords * m.wave_stats_cap));
+    HX_TRY(arena_reserve(kArenaWaveStats, sizeof(WaveStat) * m.wave_stats_cap, who, (void **)&m.wave_stats));
+    HX_TRY(arena_reserve(kArenaWaveCtr, 8ull * kWaveCtrWords * m.wave_stats_cap, who, (void **)&m.wave_ctr));
     m.inited = true;
     return HCLIB_HIP_OK;
 }
@@ -322,16 +355,16 @@ void hclib_hip_finalize(void) {
     Module &m = g_mod;
     if (!m.inited) return;
     (void)hipStreamSynchronize(m.stream);
-    if (m.pool_mem) (void)hipFree(m.pool_mem);
-    (void)hipFree(m.globals);
-    (void)hipFree(m.wave_stats);
-    (void)hipFree(m.wave_ctr);
-    if (m.seed_mem) (void)hipFree(m.seed_mem);
-    if (m.timeline) (void)hipFree(m.timeline);
+    for (Arena &a : m.arenas) dev_release(a.mem, a.bytes);
     (void)hipEventDestroy(m.ev0);
     (void)hipEventDestroy(m.ev1);
     (void)hipStreamDestroy(m.stream);
     m = Module();
+}
+
+void hclib_hip_device_memory_live(uint64_t out[2]) {
+    out[0] = g_live[0];
+    out[1] = g_live[1];
 }
 
 int hclib_hip_num_cus(void) { return g_mod.inited ? g_mod.num_cus : 0; }

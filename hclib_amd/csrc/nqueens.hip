@@ -447,8 +447,9 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
     const unsigned long long ids = bots ? p.scopes + 1 + (blocks ? (unsigned long long)grid * kScopeBlock : 0ull) : 1ull;
     const size_t jb = (sizeof(FinishScope) * (size_t)ids + 255) & ~(size_t)255;
     const size_t hb = hist ? 256 : 0;  // behind the arena's counters: n + 1 words
-    void *dmem = nullptr;
-    HX_HIP(hipMalloc(&dmem, jb + 256 + hb));
+    DevBuf buf;
+    HX_TRY(buf.alloc(jb + 256 + hb, "hclib_hip_nqueens"));
+    char *dmem = buf.p;
     NqCtx ctx;
     ctx.n = (uint32_t)n;
     ctx.full = (1u << n) - 1u;
@@ -457,58 +458,43 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
     ctx.local = env_int("HCLIB_HIP_NQUEENS_LOCAL", 1);
     ctx.blocks = blocks;
     ctx.fin.scopes = (FinishScope *)dmem;
-    ctx.fin.next = (uint32_t *)((char *)dmem + jb);
+    ctx.fin.next = (uint32_t *)(dmem + jb);
     ctx.fin.cap = (uint32_t)ids;
     ctx.fin.root_value = (unsigned long long *)(ctx.fin.next + 16);
-    ctx.hist = hist ? (unsigned long long *)((char *)dmem + jb + 256) : nullptr;
-    int rc = hip_check(hipMemsetAsync(ctx.fin.next, 0, 256 + hb, m.stream), "hipMemsetAsync");
+    ctx.hist = hist ? (unsigned long long *)(dmem + jb + 256) : nullptr;
+    HX_HIP(hipMemsetAsync(ctx.fin.next, 0, 256 + hb, m.stream));
     PoolView pool;
     SchedConfig cfg;
-    if (rc == HCLIB_HIP_OK)
-        rc = make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
-                       (uint32_t)env_int("HCLIB_HIP_NQUEENS_CHUNK", 32), 8, &pool);
-    if (rc == HCLIB_HIP_OK) {
-        // fib's unseeded settings (fib.hip): a batch pushes at most 64 * 10
-        // range items, so 256 leaves the 1,024-item ring its room
-        cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_HI", 256);
-        cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_LO", 32);
-        cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-        cfg.nwaves = (uint32_t)grid;
-        cfg.stamps = 0;
-        cfg.hunger = (uint32_t)env_int("HCLIB_HIP_NQUEENS_HUNGER", 8);
-        cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
-        rc = reset_sched(pool, 1u, false, (uint32_t)grid);
-    }
-    if (rc == HCLIB_HIP_OK) rc = hip_check(hipEventRecord(m.ev0, m.stream), "hipEventRecord");
-    if (rc == HCLIB_HIP_OK) {
-        if (bots) rc = hist ? nq_launch<NqBotsKind<true>>(ctx, pool, cfg, grid)
-                            : nq_launch<NqBotsKind<false>>(ctx, pool, cfg, grid);
-        else rc = hist ? nq_launch<NqFlatKind<true>>(ctx, pool, cfg, grid)
-                       : nq_launch<NqFlatKind<false>>(ctx, pool, cfg, grid);
-    }
-    if (rc != HCLIB_HIP_OK) {
-        (void)hipStreamSynchronize(m.stream);
-        (void)hipFree(dmem);
-        return rc;
-    }
-    rc = hip_check(hipEventRecord(m.ev1, m.stream), "hipEventRecord");
+    HX_TRY(make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
+                     (uint32_t)env_int("HCLIB_HIP_NQUEENS_CHUNK", 32), 8, &pool));
+    // fib's unseeded settings (fib.hip): a batch pushes at most 64 * 10
+    // range items, so 256 leaves the 1,024-item ring its room
+    cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_HI", 256);
+    cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_LO", 32);
+    cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
+    cfg.nwaves = (uint32_t)grid;
+    cfg.stamps = 0;
+    cfg.hunger = (uint32_t)env_int("HCLIB_HIP_NQUEENS_HUNGER", 8);
+    cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
+    HX_TRY(reset_sched(pool, 1u, false, (uint32_t)grid));
+    HX_HIP(hipEventRecord(m.ev0, m.stream));
+    if (bots) HX_TRY(hist ? nq_launch<NqBotsKind<true>>(ctx, pool, cfg, grid)
+                          : nq_launch<NqBotsKind<false>>(ctx, pool, cfg, grid));
+    else HX_TRY(hist ? nq_launch<NqFlatKind<true>>(ctx, pool, cfg, grid)
+                     : nq_launch<NqFlatKind<false>>(ctx, pool, cfg, grid));
+    HX_HIP(hipEventRecord(m.ev1, m.stream));
     SchedGlobals gl;
-    const int rcs = finish_sched(&gl, "hclib_hip_nqueens");
-    if (rc == HCLIB_HIP_OK) rc = rcs;
+    HX_TRY(finish_sched(&gl, "hclib_hip_nqueens"));
     unsigned long long v = 0, h[kNqMaxN + 1] = {};
-    if (rc == HCLIB_HIP_OK && bots)
-        rc = hip_check(hipMemcpy(&v, ctx.fin.root_value, 8, hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == HCLIB_HIP_OK && hist)
-        rc = hip_check(hipMemcpy(h, ctx.hist, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost), "hipMemcpy");
-    if (rc == HCLIB_HIP_OK && env_int("HCLIB_HIP_NQUEENS_DEBUG", 0)) {
+    if (bots) HX_HIP(hipMemcpy(&v, ctx.fin.root_value, 8, hipMemcpyDeviceToHost));
+    if (hist) HX_HIP(hipMemcpy(h, ctx.hist, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost));
+    if (env_int("HCLIB_HIP_NQUEENS_DEBUG", 0)) {
         uint32_t used = 0;  // scopes that lived in HBM (opened there or promoted from LDS)
         if (hipMemcpy(&used, ctx.fin.next, 4, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "nqueens(%d): %u of %llu scope ids taken in HBM (local %d)\n", n, used, p.scopes, ctx.local);
     }
     float ms = 0;
     (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    (void)hipFree(dmem);
-    if (rc != HCLIB_HIP_OK) return rc;
     result->solutions = bots ? v : gl.counters[3];
     result->items = gl.counters[0];
     result->joins = gl.counters[1];

@@ -42,8 +42,7 @@
 #include <map>
 #include <vector>
 
-#include "hx_module.h"
-#include "../../include/hclib_hip/hx_dyn.h"
+#include "hx_client.h"
 
 namespace hx {
 namespace {
@@ -59,7 +58,7 @@ enum : int { kCntSortLeaf = 0, kCntSortSplit = 1, kCntMergeLeaf = 2, kCntMergeSp
 
 struct SortCtx {
     long long *keys;             // [2][n]: the array, tmp
-    unsigned long long *counts;  // per task class, a 256-B line each: [0] tasks [1] ticks spent in them
+    unsigned long long *counts;  // per task class (hx_client.h class_count)
     uint32_t n, merge_cutoff, sort_cutoff;
     uint32_t sc1;  // leaves store keys write-through (sc1) and check out with a drain instead of a release
 };
@@ -67,14 +66,6 @@ struct SortCtx {
 __device__ __forceinline__ long long *sort_lds() {
     __shared__ __attribute__((aligned(16))) long long s[kSortLdsKeys];
     return s;
-}
-
-// one task of class `which` that took `ticks` of the 100 MHz clock, check-out included
-__device__ __forceinline__ void sort_count(const SortCtx &c, int which, unsigned long long ticks) {
-    if (lane_id() == 0) {
-        add_agent(&c.counts[which * 32], 1ull);
-        add_agent(&c.counts[which * 32 + 1], ticks);
-    }
 }
 
 // a key a leaf writes: a plain store, released by the check-out's fence, or
@@ -180,17 +171,10 @@ __device__ __forceinline__ uint32_t sort_binsplit(long long val, const long long
     return r[lo] > val ? lo : lo + 1;
 }
 
-struct SortKind {
-    using Ctx = SortCtx;
+struct SortKind : TimedKind<SortKind, SortCtx> {
     static constexpr bool kSc1Payload = false;  // keys move by plain loads and stores
     // payload: SORT / MERGE_PHASE {kind, lo, size, fin}
     //          MERGE {kind | src << 8, l1, e1, l2, e2, ldest, fin}: ranges [l, e) of array `src`, into the other
-    __device__ static void run(const Ctx &c, DynWave &w, uint32_t, const uint32_t *pay) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        int which = -1;
-        body(c, w, pay, which);
-        if (which >= 0) sort_count(c, which, __builtin_amdgcn_s_memrealtime() - t0);
-    }
     __device__ static void body(const Ctx &c, DynWave &w, const uint32_t *pay, int &which) {
         const uint32_t kind = pay[0] & 0xffu;
         const int lane = lane_id();
@@ -280,12 +264,7 @@ struct SortKind {
 
 __global__ __launch_bounds__(64) void k_sort(SortCtx c, DynView v) { run_dyn_worker<SortKind>(c, v); }
 
-struct SortState {
-    void *buf = nullptr;
-    size_t bytes = 0;
-    unsigned long long ticks[kCntKinds] = {};  // the last launch's, by task class
-};
-SortState g_sort;
+ClassCounters<kCntKinds> g_sort;  // the last launch's
 
 // ---------------------------------------------------------------- pool bound
 // The sort tree depends on n and sort_cutoff alone, so its SORT and MERGE_PHASE
@@ -387,20 +366,10 @@ extern "C" int hclib_hip_sort_i64(int64_t *keys, int64_t n, int merge_cutoff, in
     Module &m = mod();
 
     // [counts: a line per task class][array n][tmp n]
-    const size_t hdr = kCntKinds * 256, kbytes = (size_t)n * sizeof(int64_t), bytes = hdr + 2 * kbytes;
-    if (bytes > g_sort.bytes) {
-        if (g_sort.buf) (void)hipFree(g_sort.buf);
-        g_sort.buf = nullptr;
-        g_sort.bytes = 0;
-        if (hipMalloc(&g_sort.buf, bytes) != hipSuccess) {
-            set_error("hclib_hip_sort_i64: hipMalloc(%zu) failed", bytes);
-            return HCLIB_HIP_ENOMEM;
-        }
-        g_sort.bytes = bytes;
-    }
-    char *d = (char *)g_sort.buf;
-    HX_HIP(hipMemsetAsync(d, 0, hdr, m.stream));
-    // (`keys` outlives the copy: the stream is synchronised before the call returns)
+    const size_t hdr = g_sort.kBytes, kbytes = (size_t)n * sizeof(int64_t), bytes = hdr + 2 * kbytes;
+    char *d = nullptr;
+    HX_TRY(arena_reserve(kArenaSort, bytes, "hclib_hip_sort_i64", (void **)&d));
+    // (`keys` outlives the copy: launch_dyn synchronises the stream)
     HX_HIP(hipMemcpyAsync(d + hdr, keys, kbytes, hipMemcpyHostToDevice, m.stream));
 
     SortCtx c;
@@ -412,40 +381,28 @@ extern "C" int hclib_hip_sort_i64(int64_t *keys, int64_t n, int merge_cutoff, in
     // (HCLIB_HIP_SORT_SC1=0: plain stores and a release fence per leaf, measured slower)
     c.sc1 = env_int("HCLIB_HIP_SORT_SC1", 1) ? 1u : 0u;
     const uint32_t root[kSortWords] = {kSortTask, 0u, (uint32_t)n, kDynOpen, 0, 0, 0, 0};
-    hclib_hip_dyn_launch_t L;
     // (HCLIB_HIP_SORT_WAVES_PER_CU: for measurements; 8 waves of 16 KB fill the LDS best)
     int wpc = env_int("HCLIB_HIP_SORT_WAVES_PER_CU", kSortWavesPerCu);
     wpc = wpc < 1 ? 1 : (wpc > kSortWavesPerCu ? kSortWavesPerCu : wpc);
-    int rc = hclib_hip_dyn_begin(kSortWords, root, 1, (uint32_t)cap[0], (uint32_t)cap[1], (uint32_t)cap[2], wpc, 0,
-                                 &L);
-    if (rc) {
-        (void)hipStreamSynchronize(m.stream);
-        return rc;
-    }
-    const DynView v = *(const DynView *)L.view;
-    // (no residency check: a dyn worker waits only for ready-list slots below
-    // the tail, which waves that already run fill; one that starts late joins in)
-    hipLaunchKernelGGL(k_sort, dim3(L.grid), dim3(64), 0, m.stream, c, v);
     hclib_hip_dyn_stats_t st{};
-    const int rc_end = hclib_hip_dyn_end("hclib_hip_sort_i64", &st);
     uint64_t fin[2] = {0, 0};
-    hclib_hip_dyn_finish_stats(fin);
-    unsigned long long cnt[kCntKinds * 32] = {};
-    if (hipMemcpy(cnt, c.counts, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) memset(cnt, 0, sizeof(cnt));
+    const int rc = launch_dyn(kSortWords, root, cap[0], cap[1], cap[2], wpc, "hclib_hip_sort_i64", d, g_sort, &st, fin,
+                              [&](int grid, const DynView &v) {
+                                  hipLaunchKernelGGL(k_sort, dim3(grid), dim3(64), 0, m.stream, c, v);
+                              });
     if (result) {
         result->tasks = st.tasks;
-        result->sort_leaf = cnt[kCntSortLeaf * 32];
-        result->sort_split = cnt[kCntSortSplit * 32];
-        result->merge_leaf = cnt[kCntMergeLeaf * 32];
-        result->merge_split = cnt[kCntMergeSplit * 32];
-        result->merge_empty = cnt[kCntMergeEmpty * 32];
+        result->sort_leaf = g_sort.tasks[kCntSortLeaf];
+        result->sort_split = g_sort.tasks[kCntSortSplit];
+        result->merge_leaf = g_sort.tasks[kCntMergeLeaf];
+        result->merge_split = g_sort.tasks[kCntMergeSplit];
+        result->merge_empty = g_sort.tasks[kCntMergeEmpty];
         result->finishes = fin[0];
         result->check_ins = fin[1];
         result->kernel_ms = st.kernel_ms;
         result->keys_per_s = st.kernel_ms > 0 ? (double)n / (st.kernel_ms * 1e-3) : 0.0;
     }
-    for (int k = 0; k < kCntKinds; ++k) g_sort.ticks[k] = cnt[k * 32 + 1];
-    if (rc_end) return rc_end;
+    if (rc) return rc;
     HX_HIP(hipMemcpy(keys, c.keys, kbytes, hipMemcpyDeviceToHost));
     return HCLIB_HIP_OK;
 }

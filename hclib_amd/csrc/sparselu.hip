@@ -52,8 +52,7 @@
 #include <new>
 #include <vector>
 
-#include "hx_module.h"
-#include "../../include/hclib_hip/hx_dag.h"
+#include "hx_client.h"
 
 namespace hx {
 namespace {
@@ -339,13 +338,8 @@ __device__ __forceinline__ void slu_solve(const float *diag, float *X, int B) {
     slu_block_out<!FWD>(X, V, B);
 }
 
-struct SluKind {
-    using Ctx = SluCtx;
+struct SluKind : OnePromiseKind<SluCtx> {
     static constexpr bool kSc1Payload = true;  // blocks move by ld_agent / st_agent only (ldt / stt)
-    // one promise per task, the block version it makes: run_dag_group's split put
-    static constexpr int kPutN = 1;
-    __device__ static void promises(const Ctx &, uint32_t t, uint32_t (&p)[1]) { p[0] = t; }
-    __device__ static void datums(const Ctx &, uint32_t, unsigned long long (&d)[1]) { d[0] = 0ull; }
     __device__ static bool run_group(const Ctx &c, uint32_t, const uint32_t *pl, int) {
         const uint32_t kind = pl[0], kk = pl[1], ii = pl[2], jj = pl[3];
         const int B = c.B;
@@ -371,29 +365,10 @@ __global__ __launch_bounds__(kSluThreads, 2) void k_sparselu_bmod_rate(float *bu
     }
 }
 
-struct SluState {
-    void *buf = nullptr;
-    size_t bytes = 0;
-};
-SluState g_slu;
-
-int slu_reserve(size_t bytes, const char *who) {
-    if (bytes <= g_slu.bytes) return HCLIB_HIP_OK;
-    if (g_slu.buf) (void)hipFree(g_slu.buf);
-    g_slu.buf = nullptr;
-    g_slu.bytes = 0;
-    if (hipMalloc(&g_slu.buf, bytes) != hipSuccess) {
-        set_error("%s: hipMalloc(%zu) failed", who, bytes);
-        return HCLIB_HIP_ENOMEM;
-    }
-    g_slu.bytes = bytes;
-    return HCLIB_HIP_OK;
-}
-
 struct SluPlan {
     std::vector<uint8_t> mask;  // the final structure
     uint64_t counts[6] = {0, 0, 0, 0, 0, 0};  // lu0, fwd, bdiv, bmod, blocks in, blocks out
-    std::vector<uint32_t> payload, off, ids;  // filled when `graph`
+    VersionGraph graph;  // filled when `graph`
 };
 
 // The symbolic pass, in two parts. First the structure and the counts alone,
@@ -404,9 +379,7 @@ struct SluPlan {
 // is rejected here, before any graph array grows. Then, if asked for, the graph
 // in the reference's program order (sparselu.ref.c:300-322). Step kk only
 // creates blocks with both indices above kk, so the blocks of row kk and of
-// column kk that step kk meets are those of the final structure. `last` is the
-// task that made each block's newest version (none: version 0, the host's
-// upload or a zeroed fill-in block).
+// column kk that step kk meets are those of the final structure.
 int slu_plan(const uint8_t *mask, int S, bool graph, SluPlan &p, const char *who) {
     if (!mask) {
         set_error("%s: mask must not be NULL", who);
@@ -462,43 +435,26 @@ int slu_plan(const uint8_t *mask, int S, bool graph, SluPlan &p, const char *who
             for (size_t jj = 0; jj < n; ++jj) p.counts[5] += p.mask[ii * n + jj] = (uint8_t)has(ii, jj);
         if (!graph) return HCLIB_HIP_OK;
 
-        const uint32_t none = 0xffffffffu;
-        std::vector<uint32_t> last(nn, none);
-        std::vector<size_t> rows, cols;
-        p.payload.reserve((size_t)ntasks * 4);
-        p.off.reserve((size_t)ntasks + 1);
-        p.off.push_back(0);
-        auto task = [&](uint32_t kind, size_t kk, size_t ii, size_t jj, const size_t *in, int nin) {
-            const uint32_t id = (uint32_t)(p.off.size() - 1);
-            const uint32_t pl[4] = {kind, (uint32_t)kk, (uint32_t)ii, (uint32_t)jj};
-            p.payload.insert(p.payload.end(), pl, pl + 4);
-            for (int q = 0; q < nin; ++q)
-                if (last[in[q]] != none) p.ids.push_back(last[in[q]]);
-            p.off.push_back((uint32_t)p.ids.size());
-            last[in[0]] = id;  // in[0] is the block the task writes
-        };
-        for (size_t kk = 0; kk < n; ++kk) {
+        VersionGraph &g = p.graph = VersionGraph(nn);
+        std::vector<uint32_t> rows, cols;
+        g.reserve((size_t)ntasks, 0);  // (the awaits grow as they come: a plan may be all there is memory for)
+        for (uint32_t kk = 0; kk < n; ++kk) {
             const size_t d = kk * n + kk;
-            task(kSluLu0, kk, kk, kk, &d, 1);
+            g.task(kSluLu0, kk, kk, kk, d, {d});
             rows.clear();
             cols.clear();
-            for (size_t jj = kk + 1; jj < n; ++jj)
+            for (uint32_t jj = kk + 1; jj < n; ++jj)
                 if (p.mask[kk * n + jj]) {
-                    const size_t in[2] = {kk * n + jj, d};
-                    task(kSluFwd, kk, kk, jj, in, 2);
+                    g.task(kSluFwd, kk, kk, jj, kk * n + jj, {kk * n + jj, d});
                     cols.push_back(jj);
                 }
-            for (size_t ii = kk + 1; ii < n; ++ii)
+            for (uint32_t ii = kk + 1; ii < n; ++ii)
                 if (p.mask[ii * n + kk]) {
-                    const size_t in[2] = {ii * n + kk, d};
-                    task(kSluBdiv, kk, ii, kk, in, 2);
+                    g.task(kSluBdiv, kk, ii, kk, ii * n + kk, {ii * n + kk, d});
                     rows.push_back(ii);
                 }
-            for (size_t ii : rows)
-                for (size_t jj : cols) {
-                    const size_t in[3] = {ii * n + jj, ii * n + kk, kk * n + jj};
-                    task(kSluBmod, kk, ii, jj, in, 3);
-                }
+            for (uint32_t ii : rows)
+                for (uint32_t jj : cols) g.task(kSluBmod, kk, ii, jj, ii * n + jj, {ii * n + jj, ii * n + kk, kk * n + jj});
         }
     } catch (const std::bad_alloc &) {
         set_error("%s: out of host memory for the plan of %d x %d blocks", who, S, S);
@@ -565,9 +521,10 @@ extern "C" int hclib_hip_sparselu_plan(const uint8_t *mask, int S, uint8_t *mask
     if (mask_out) memcpy(mask_out, p.mask.data(), p.mask.size());
     if (counts) memcpy(counts, p.counts, sizeof(p.counts));
     if (graph) {
-        memcpy(payload, p.payload.data(), p.payload.size() * sizeof(uint32_t));
-        memcpy(await_off, p.off.data(), p.off.size() * sizeof(uint32_t));
-        if (!p.ids.empty()) memcpy(await_ids, p.ids.data(), p.ids.size() * sizeof(uint32_t));
+        const VersionGraph &g = p.graph;
+        memcpy(payload, g.payload.data(), g.payload.size() * sizeof(uint32_t));
+        memcpy(await_off, g.off.data(), g.off.size() * sizeof(uint32_t));
+        if (!g.ids.empty()) memcpy(await_ids, g.ids.data(), g.ids.size() * sizeof(uint32_t));
     }
     return HCLIB_HIP_OK;
 }
@@ -585,7 +542,6 @@ static int slu_run(const uint8_t *mask, const float *blocks, int S, int B, uint8
     }
     SluPlan p;
     HX_TRY(slu_plan(mask, S, true, p, "hclib_hip_sparselu"));
-    const uint64_t ntasks = p.counts[0] + p.counts[1] + p.counts[2] + p.counts[3];
     HX_TRY(ensure_device());
     Module &m = mod();
 
@@ -602,13 +558,14 @@ static int slu_run(const uint8_t *mask, const float *blocks, int S, int B, uint8
         if (mask[e]) memcpy(hb + out_pos * B2, blocks + in_pos++ * B2, B2 * sizeof(float));
         if (p.mask[e]) ++out_pos;
     }
-    HX_TRY(slu_reserve(bytes, "hclib_hip_sparselu"));
-    // (`h` outlives the copy: the stream is synchronised before it goes)
-    HX_HIP(hipMemcpyAsync(g_slu.buf, h.data(), bytes, hipMemcpyHostToDevice, m.stream));
+    char *buf = nullptr;
+    HX_TRY(arena_reserve(kArenaSparselu, bytes, "hclib_hip_sparselu", (void **)&buf));
+    // (`h` outlives the copy: launch_dag_group synchronises the stream)
+    HX_HIP(hipMemcpyAsync(buf, h.data(), bytes, hipMemcpyHostToDevice, m.stream));
 
     SluCtx c;
-    c.blocks = (float *)g_slu.buf;
-    c.slot = (const int *)((char *)g_slu.buf + o_slot);
+    c.blocks = (float *)buf;
+    c.slot = (const int *)(buf + o_slot);
     c.S = S;
     c.B = B;
     int wgs = env_int("HCLIB_HIP_SPARSELU_WGS", kSluWgsPerCu);
@@ -618,23 +575,14 @@ static int slu_run(const uint8_t *mask, const float *blocks, int S, int B, uint8
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *)k_sparselu, kSluThreads, 0) == hipSuccess &&
         per_cu >= 1 && wgs > per_cu)
         wgs = per_cu;
-    hclib_hip_dag_launch_t L;
-    int rc = hclib_hip_dag_begin((uint32_t)ntasks, (uint32_t)ntasks, 4, p.payload.data(), p.off.data(), p.ids.data(),
-                                 nullptr, nullptr, wgs, 0, &L);
-    if (rc) {
-        (void)hipStreamSynchronize(m.stream);
-        return rc;
-    }
-    const DagView &v = *(const DagView *)L.view;
     // (no body reports a device error of its own: the launch's error word,
     // run_dag_group's, is checked by hclib_hip_dag_end)
-    rc = check_resident((const void *)k_sparselu, L.grid, kSluThreads, 0, "hclib_hip_sparselu");
-    if (rc == HCLIB_HIP_OK) hipLaunchKernelGGL(k_sparselu, dim3(L.grid), dim3(kSluThreads), 0, m.stream, c, v);
     hclib_hip_dag_stats_t st{};
-    const int rc_end = hclib_hip_dag_end("hclib_hip_sparselu", nullptr, nullptr, &st);
-    if (rc) return rc;  // nothing was launched; dag_end closed the launch
-    if (rc_end) return rc_end;
-    HX_HIP(hipMemcpy(blocks_out, g_slu.buf, nout * B2 * sizeof(float), hipMemcpyDeviceToHost));
+    HX_TRY(launch_dag_group(p.graph, wgs, (const void *)k_sparselu, kSluThreads, "hclib_hip_sparselu", &st,
+                            [&](int grid, const DagView &v) {
+                                hipLaunchKernelGGL(k_sparselu, dim3(grid), dim3(kSluThreads), 0, m.stream, c, v);
+                            }));
+    HX_HIP(hipMemcpy(blocks_out, buf, nout * B2 * sizeof(float), hipMemcpyDeviceToHost));
     memcpy(mask_out, p.mask.data(), nn);
     if (result) {
         result->blocks_in = p.counts[4];
@@ -679,12 +627,13 @@ extern "C" int hclib_hip_sparselu_bmod_rate(int B, int wgs_per_cu, int reps, dou
         x = x * 1664525u + 1013904223u;
         h[e] = ((float)(x >> 8) / 8388608.0f - 1.0f) / (float)B;
     }
-    HX_TRY(slu_reserve(nfloats * sizeof(float), "hclib_hip_sparselu_bmod_rate"));
-    HX_HIP(hipMemcpy(g_slu.buf, h.data(), nfloats * sizeof(float), hipMemcpyHostToDevice));
+    float *buf = nullptr;
+    HX_TRY(arena_reserve(kArenaSparselu, nfloats * sizeof(float), "hclib_hip_sparselu_bmod_rate", (void **)&buf));
+    HX_HIP(hipMemcpy(buf, h.data(), nfloats * sizeof(float), hipMemcpyHostToDevice));
     HX_TRY(check_resident((const void *)k_sparselu_bmod_rate, grid, kSluThreads, 0, "hclib_hip_sparselu_bmod_rate"));
-    hipLaunchKernelGGL(k_sparselu_bmod_rate, dim3(grid), dim3(kSluThreads), 0, m.stream, (float *)g_slu.buf, B, 1);
+    hipLaunchKernelGGL(k_sparselu_bmod_rate, dim3(grid), dim3(kSluThreads), 0, m.stream, buf, B, 1);
     HX_HIP(hipEventRecord(m.ev0, m.stream));
-    hipLaunchKernelGGL(k_sparselu_bmod_rate, dim3(grid), dim3(kSluThreads), 0, m.stream, (float *)g_slu.buf, B, reps);
+    hipLaunchKernelGGL(k_sparselu_bmod_rate, dim3(grid), dim3(kSluThreads), 0, m.stream, buf, B, reps);
     HX_HIP(hipEventRecord(m.ev1, m.stream));
     HX_HIP(hipEventSynchronize(m.ev1));
     float t = 0;

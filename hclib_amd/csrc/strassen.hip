@@ -69,8 +69,7 @@
 // doubles, bands split by rows, tiles are 512 bytes wide.
 #include <string.h>
 
-#include "hx_module.h"
-#include "../../include/hclib_hip/hx_dyn.h"
+#include "hx_client.h"
 
 namespace hx {
 namespace {
@@ -92,7 +91,7 @@ enum : int { kCntBase = 0, kCntPre = 1, kCntCombine = 2, kCntSplit = 3, kCntFork
 
 struct StrCtx {
     double *m;                   // the arena: A, B, C, then the regions of temporaries
-    unsigned long long *counts;  // per task class, a 256-B line each: [0] tasks [1] ticks spent in them
+    unsigned long long *counts;  // per task class (hx_client.h class_count)
     unsigned long long total;    // elements of the arena
     unsigned long long region[kStrMaxLevels];  // element offset of each level's region
     uint32_t cutoff, band_rows;
@@ -101,13 +100,6 @@ struct StrCtx {
 __device__ __forceinline__ double *str_lds() {
     __shared__ __attribute__((aligned(16))) double s[kStrKc * (kStrTile + 2) + kStrKc * kStrTile];
     return s;
-}
-
-__device__ __forceinline__ void str_count(const StrCtx &c, int which, unsigned long long ticks) {
-    if (lane_id() == 0) {
-        add_agent(&c.counts[which * 32], 1ull);
-        add_agent(&c.counts[which * 32 + 1], ticks);
-    }
 }
 
 // two doubles at a 16-byte aligned address: a plain store, released by the
@@ -248,19 +240,13 @@ __device__ __forceinline__ bool str_in(const StrCtx &c, uint32_t off, uint32_t l
 }
 
 template <bool SC1>
-struct StrKind {
+struct StrKind : TimedKind<StrKind<SC1>, StrCtx> {
     using Ctx = StrCtx;
     static constexpr bool kSc1Payload = false;  // doubles move by plain loads behind the worker's acquire
     // payload: MUL / FORK / POST {kind, C, ldc, A, lda, B, ldb, size, fin, level, path}
     //          TILE              {kind, C, ldc, A, lda, B, ldb, K, fin}: 64 x 64 of C, all offsets the tile's
     //          PRE               {kind, A, lda, B, ldb, W, q, row0, rows, f0}
     //          COMBINE           {kind, C, ldc, W, q, row0, rows, fin}
-    __device__ static void run(const Ctx &c, DynWave &w, uint32_t, const uint32_t *pay) {
-        const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-        int which = -1;
-        body(c, w, pay, which);
-        if (which >= 0) str_count(c, which, __builtin_amdgcn_s_memrealtime() - t0);
-    }
     __device__ static void bad(DynWave &w) {
         if (lane_id() == 0) dev_error(dyn_err(w.v), kErrBadTask);
     }
@@ -388,12 +374,7 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(2))) void k_
     run_dyn_worker<StrKind<SC1>>(c, v);
 }
 
-struct StrState {
-    void *buf = nullptr;
-    size_t bytes = 0;
-    unsigned long long ticks[kCntKinds] = {};  // the last launch's, by task class
-};
-StrState g_str;
+ClassCounters<kCntKinds> g_str;  // the last launch's
 
 // The call tree is a function of (n, cutoff, band_rows) alone: every count is exact.
 struct StrPlan {
@@ -505,23 +486,15 @@ extern "C" int hclib_hip_strassen(const double *a, const double *b, double *c, i
     Module &m = mod();
 
     // [counts: a line per task class][A][B][C][the temporaries, a region per level]
-    const size_t hdr = kCntKinds * 256, nn = (size_t)n * n, mbytes = nn * sizeof(double);
+    const size_t hdr = g_str.kBytes, nn = (size_t)n * n, mbytes = nn * sizeof(double);
     const size_t bytes = hdr + (3 * nn + (size_t)p.ws) * sizeof(double);
-    if (bytes > g_str.bytes) {
-        if (g_str.buf) (void)hipFree(g_str.buf);
-        g_str.buf = nullptr;
-        g_str.bytes = 0;
-        if (hipMalloc(&g_str.buf, bytes) != hipSuccess) {
-            (void)hipGetLastError();
-            set_error("hclib_hip_strassen: hipMalloc(%zu) failed (n = %d, cutoff = %d: %llu bytes of temporaries)",
-                      bytes, n, cutoff, p.ws * 8ull);
-            return HCLIB_HIP_ENOMEM;
-        }
-        g_str.bytes = bytes;
+    char *d = nullptr;
+    if (const int rc = arena_reserve(kArenaStrassen, bytes, "hclib_hip_strassen", (void **)&d)) {
+        set_error("hclib_hip_strassen: hipMalloc(%zu) failed (n = %d, cutoff = %d: %llu bytes of temporaries)", bytes, n,
+                  cutoff, p.ws * 8ull);
+        return rc;
     }
-    char *d = (char *)g_str.buf;
-    HX_HIP(hipMemsetAsync(d, 0, hdr, m.stream));
-    // (`a` and `b` outlive the copies: the stream is synchronised before the call returns)
+    // (`a` and `b` outlive the copies: launch_dyn synchronises the stream)
     HX_HIP(hipMemcpyAsync(d + hdr, a, mbytes, hipMemcpyHostToDevice, m.stream));
     HX_HIP(hipMemcpyAsync(d + hdr + mbytes, b, mbytes, hipMemcpyHostToDevice, m.stream));
 
@@ -536,42 +509,30 @@ extern "C" int hclib_hip_strassen(const double *a, const double *b, double *c, i
     const bool sc1 = env_int("HCLIB_HIP_STRASSEN_SC1", 1) != 0;
     const uint32_t un = (uint32_t)n;
     const uint32_t root[kStrWords] = {kStrMul, 2u * un * un, un, 0u, un, un * un, un, un, kDynOpen, 0u, 0u, 0u};
-    hclib_hip_dyn_launch_t L;
     // (HCLIB_HIP_STRASSEN_WAVES_PER_CU: for measurements)
     int wpc = env_int("HCLIB_HIP_STRASSEN_WAVES_PER_CU", str_waves_per_cu(n, cutoff));
     wpc = wpc < 1 ? 1 : (wpc > kStrWavesPerCu ? kStrWavesPerCu : wpc);
-    int rc = hclib_hip_dyn_begin(kStrWords, root, 1, (uint32_t)p.tasks, (uint32_t)p.scopes,
-                                 (uint32_t)(p.nodes ? p.nodes : 1), wpc, 0, &L);
-    if (rc) {
-        (void)hipStreamSynchronize(m.stream);
-        return rc;
-    }
-    const DynView v = *(const DynView *)L.view;
-    // (no residency check: a dyn worker waits only for ready-list slots below
-    // the tail, which waves that already run fill; one that starts late joins in)
-    if (sc1) hipLaunchKernelGGL(k_strassen<true>, dim3(L.grid), dim3(64), 0, m.stream, cx, v);
-    else hipLaunchKernelGGL(k_strassen<false>, dim3(L.grid), dim3(64), 0, m.stream, cx, v);
     hclib_hip_dyn_stats_t st{};
-    const int rc_end = hclib_hip_dyn_end("hclib_hip_strassen", &st);
     uint64_t fin[2] = {0, 0};
-    hclib_hip_dyn_finish_stats(fin);
-    unsigned long long cnt[kCntKinds * 32] = {};
-    if (hipMemcpy(cnt, cx.counts, sizeof(cnt), hipMemcpyDeviceToHost) != hipSuccess) memset(cnt, 0, sizeof(cnt));
+    const int rc = launch_dyn(kStrWords, root, p.tasks, p.scopes, p.nodes ? p.nodes : 1, wpc, "hclib_hip_strassen", d,
+                              g_str, &st, fin, [&](int grid, const DynView &v) {
+                                  if (sc1) hipLaunchKernelGGL(k_strassen<true>, dim3(grid), dim3(64), 0, m.stream, cx, v);
+                                  else hipLaunchKernelGGL(k_strassen<false>, dim3(grid), dim3(64), 0, m.stream, cx, v);
+                              });
     if (result) {
         result->tasks = st.tasks;
-        result->splits = cnt[kCntSplit * 32];
-        result->base = cnt[kCntBase * 32];
-        result->tiles = cnt[kCntTile * 32];
-        result->pre_bands = cnt[kCntPre * 32];
-        result->combine_bands = cnt[kCntCombine * 32];
+        result->splits = g_str.tasks[kCntSplit];
+        result->base = g_str.tasks[kCntBase];
+        result->tiles = g_str.tasks[kCntTile];
+        result->pre_bands = g_str.tasks[kCntPre];
+        result->combine_bands = g_str.tasks[kCntCombine];
         result->finishes = fin[0];
         result->check_ins = fin[1];
         result->workspace_bytes = p.ws * sizeof(double);
         result->kernel_ms = st.kernel_ms;
         result->gflops = st.kernel_ms > 0 ? 2.0 * n * (double)n * n / (st.kernel_ms * 1e6) : 0.0;
     }
-    for (int k = 0; k < kCntKinds; ++k) g_str.ticks[k] = cnt[k * 32 + 1];
-    if (rc_end) return rc_end;
+    if (rc) return rc;
     HX_HIP(hipMemcpy(c, cx.m + 2 * nn, mbytes, hipMemcpyDeviceToHost));
     return HCLIB_HIP_OK;
 }

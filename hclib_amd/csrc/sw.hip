@@ -1869,11 +1869,9 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t total = al(b_s1) + al(b_s2) + al(b_bot) + al(b_right) + al(b_c) + al(b_dep) +
                          al(b_ready) + al(b_gbot) + al(b_gright) + al(b_gc) + 1024;
-    char *d = nullptr;
-    if (hipMalloc((void **)&d, total) != hipSuccess) {
-        set_error("hclib_hip_sw: hipMalloc(%zu) failed", total);
-        return HCLIB_HIP_ENOMEM;
-    }
+    DevBuf buf;
+    HX_TRY(buf.alloc(total, "hclib_hip_sw"));
+    char *d = buf.p;
     SwCtx c;
     size_t off = 0;
     c.s1 = (const int8_t *)(d + off); off += al(b_s1);
@@ -1906,21 +1904,17 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
     c.dtrace = nullptr;
     c.form = form;
     c.bh = bh;
-    int rc = HCLIB_HIP_OK;
-    auto fail = [&](int r) { (void)hipFree(d); return r; };
-    if ((rc = hip_check(hipMemcpyAsync((void *)c.s1, s1, b_s1, hipMemcpyHostToDevice, m.stream), "copy s1"))) return fail(rc);
-    if ((rc = hip_check(hipMemcpyAsync((void *)c.s2, s2, b_s2, hipMemcpyHostToDevice, m.stream), "copy s2"))) return fail(rc);
-    if ((rc = hip_check(hipMemsetAsync(misc, 0, 1024, m.stream), "memset"))) return fail(rc);
+    HX_HIP(hipMemcpyAsync((void *)c.s1, s1, b_s1, hipMemcpyHostToDevice, m.stream));
+    HX_HIP(hipMemcpyAsync((void *)c.s2, s2, b_s2, hipMemcpyHostToDevice, m.stream));
+    HX_HIP(hipMemsetAsync(misc, 0, 1024, m.stream));
     {
         uint32_t one = 1;  // tile 0 already sits at ready[0]
-        if ((rc = hip_check(hipMemcpyAsync(c.ready_tail, &one, 4, hipMemcpyHostToDevice, m.stream), "tail"))) return fail(rc);
+        HX_HIP(hipMemcpyAsync(c.ready_tail, &one, 4, hipMemcpyHostToDevice, m.stream));
     }
     if (rows || pk) {
         // every granule's tag starts at 0 (not yet put)
-        if ((rc = hip_check(hipMemsetAsync(c.gbot, 0, b_gbot, m.stream), "memset granules"))) return fail(rc);
-        if (pk && (rc = hip_check(hipMemsetAsync(c.gright, 0, al(b_gright) + b_gc, m.stream),
-                                  "memset granules")))
-            return fail(rc);
+        HX_HIP(hipMemsetAsync(c.gbot, 0, b_gbot, m.stream));
+        if (pk) HX_HIP(hipMemsetAsync(c.gright, 0, al(b_gright) + b_gc, m.stream));
     }
     if (!rows) {
         hipLaunchKernelGGL(k_sw_init, dim3(1024), dim3(256), 0, m.stream, c.deps, c.ready, c.ntw, c.nth);
@@ -1928,7 +1922,10 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
     const size_t lds = band ? sw_band_lds_bytes(th / bh)
                             : 2 * (size_t)(((tw + 1 + 3) & ~3) * 4) + 68 * 4 + 2 * (size_t)((tw + 3) & ~3) + 16 +
                                   (rows ? 2 * (size_t)(((th + 3) & ~3) * 4) : 0);
-    if (lds > 160 * 1024) return fail((set_error("hclib_hip_sw: tile too large for LDS"), HCLIB_HIP_EINVAL));
+    if (lds > 160 * 1024) {
+        set_error("hclib_hip_sw: tile too large for LDS");
+        return HCLIB_HIP_EINVAL;
+    }
     int per_cu = (int)((160 * 1024) / lds);
     // rows: one wave per CU owns tile rows (all resident, so every wait ends)
     int wpc = env_int("HCLIB_HIP_SW_WAVES_PER_CU", rows ? 1 : 2);
@@ -1958,11 +1955,10 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         // kernel applies (HCLIB_HIP_SW_DAG_WAVE=1: one wave per tile)
         const bool wg = band_shape && env_int("HCLIB_HIP_SW_DAG_WAVE", 0) == 0;
         hclib_hip_dag_launch_t L;
-        if ((rc = hclib_hip_dag_begin((uint32_t)nt, (uint32_t)(3 * nt), 0, nullptr, off.data(), ids.data(), nullptr,
-                                      nullptr, pk ? env_int("HCLIB_HIP_SW_PK_WGS_PER_CU", 1)
-                                                  : (wg ? env_int("HCLIB_HIP_SW_DAG_WGS_PER_CU", 1) : wpc),
-                                      c.spin_ms, &L)))
-            return fail(rc);
+        HX_TRY(hclib_hip_dag_begin((uint32_t)nt, (uint32_t)(3 * nt), 0, nullptr, off.data(), ids.data(), nullptr,
+                                   nullptr, pk ? env_int("HCLIB_HIP_SW_PK_WGS_PER_CU", 1)
+                                               : (wg ? env_int("HCLIB_HIP_SW_DAG_WGS_PER_CU", 1) : wpc),
+                                   c.spin_ms, &L));
         if (pk) {
             const size_t plds = sw_pk_lds_bytes(tw);
             c.dtrace = ((const DagView *)L.view)->trace;
@@ -1981,9 +1977,9 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         }
         // (the packed body's tagged puts are checked for double puts here)
         std::vector<uint8_t> sat(pk ? 3 * nt : 0);
-        if ((rc = hclib_hip_dag_end("hclib_hip_sw (dag)", nullptr, pk ? sat.data() : nullptr, &dst))) return fail(rc);
+        HX_TRY(hclib_hip_dag_end("hclib_hip_sw (dag)", nullptr, pk ? sat.data() : nullptr, &dst));
     } else {
-        if ((rc = hip_check(hipEventRecord(m.ev0, m.stream), "event"))) return fail(rc);
+        HX_HIP(hipEventRecord(m.ev0, m.stream));
         if (band) {
             const int k = sw_band_rows_per_wg(th, bh), nblk = ((int)nth + k - 1) / k;
             const int g = nblk < m.num_cus ? nblk : m.num_cus;
@@ -1994,13 +1990,13 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         } else if (rows && c.progressive) hipLaunchKernelGGL(k_sw_rows<true>, dim3(grid), dim3(64), lds, m.stream, c);
         else if (rows) hipLaunchKernelGGL(k_sw_rows<false>, dim3(grid), dim3(64), lds, m.stream, c);
         else hipLaunchKernelGGL(k_sw, dim3(grid), dim3(64), lds, m.stream, c);
-        if ((rc = hip_check(hipGetLastError(), "k_sw launch"))) return fail(rc);
-        if ((rc = hip_check(hipEventRecord(m.ev1, m.stream), "event"))) return fail(rc);
+        HX_HIP(hipGetLastError());
+        HX_HIP(hipEventRecord(m.ev1, m.stream));
     }
     uint32_t herr = 0;
     unsigned long long st[10] = {0};
     int corner = 0;
-    if ((rc = hip_check(hipStreamSynchronize(m.stream), "k_sw"))) return fail(rc);
+    HX_HIP(hipStreamSynchronize(m.stream));
     (void)hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost);
     (void)hipMemcpy(st, c.stats, sizeof(st), hipMemcpyDeviceToHost);
     if (HX_STAMPS && (band || (dag && band_shape))) {
@@ -2039,7 +2035,6 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
     }
     float ms = 0;
     (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    (void)hipFree(d);
     if (herr) {
         set_error("hclib_hip_sw: device error %u", herr);
         return HCLIB_HIP_EDEVICE;

@@ -742,22 +742,20 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // cost ~1 ms of libm on the host for a GEO tree (100 threshold searches
     // per depth): the last set and its device copy are kept for the next
     // search of the same tree (every call returns with the stream drained, so
-    // no launch still reads them when they are replaced)
+    // no launch still reads them when they are replaced). The host copy is
+    // valid while the device copy's arena is: Module::uts_tables_cached goes
+    // with the arena at hclib_hip_finalize
     static struct {
-        bool have = false;
-        int device = -1;
         hclib_hip_uts_params_t p;
         UtsTables T;
-        void *dmem = nullptr;
     } tab;
-    if (!tab.have || tab.device != m.device || memcmp(&tab.p, params, sizeof(tab.p)) != 0) {
-        if (tab.dmem && tab.device == m.device) (void)hipFree(tab.dmem);
-        tab.have = false;
-        tab.dmem = nullptr;
+    if (!m.uts_tables_cached || memcmp(&tab.p, params, sizeof(tab.p)) != 0) {
+        m.uts_tables_cached = false;
         HX_TRY(build_tables(*params, tab.T));
         const size_t rb = tab.T.rules.size() * sizeof(int4), tb = tab.T.thr.size() * 4;
-        HX_HIP(hipMalloc(&tab.dmem, ((rb + 255) & ~(size_t)255) + ((tb + 255) & ~(size_t)255) + kUtsBuckets + 256));
-        char *dp = (char *)tab.dmem;
+        char *dp = nullptr;
+        HX_TRY(arena_reserve(kArenaUtsTables, ((rb + 255) & ~(size_t)255) + ((tb + 255) & ~(size_t)255) + kUtsBuckets + 256,
+                             "hclib_hip_uts_search", (void **)&dp));
         HX_HIP(hipMemcpy(dp, tab.T.rules.data(), rb, hipMemcpyHostToDevice));
         HX_HIP(hipMemcpy(dp + ((rb + 255) & ~(size_t)255), tab.T.thr.data(), tb, hipMemcpyHostToDevice));
         uint8_t nb[kUtsBuckets] = {0};
@@ -765,19 +763,18 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
         HX_HIP(hipMemcpy(dp + ((rb + 255) & ~(size_t)255) + ((tb + 255) & ~(size_t)255), nb, kUtsBuckets,
                          hipMemcpyHostToDevice));
         tab.p = *params;
-        tab.device = m.device;
-        tab.have = true;
+        m.uts_tables_cached = true;
     }
     const UtsTables &T = tab.T;
-    int4 *d_rules = (int4 *)tab.dmem;
-    uint32_t *d_thr = (uint32_t *)((char *)tab.dmem + ((T.rules.size() * sizeof(int4) + 255) & ~(size_t)255));
+    int4 *d_rules = (int4 *)m.arenas[kArenaUtsTables].mem;
+    uint32_t *d_thr = (uint32_t *)((char *)d_rules + ((T.rules.size() * sizeof(int4) + 255) & ~(size_t)255));
     const uint32_t *d_nb = (const uint32_t *)((char *)d_thr + ((T.thr.size() * 4 + 255) & ~(size_t)255));
 
     // the optional per-level histogram
     const size_t hb = (size_t)max_levels * 8;
-    void *dmem = nullptr;
-    if (max_levels) HX_HIP(hipMalloc(&dmem, hb));
-    unsigned long long *d_hist = (unsigned long long *)dmem;
+    DevBuf hist_buf, chain_buf;
+    if (max_levels) HX_TRY(hist_buf.alloc(hb, "hclib_hip_uts_search"));
+    unsigned long long *d_hist = (unsigned long long *)hist_buf.p;
     const int trace_kind = max_levels > 0 ? env_int("HCLIB_HIP_UTS_TRACE", 0) : 0;
     const bool trace = trace_kind != 0;
     if (max_levels) HX_HIP(hipMemsetAsync(d_hist, trace ? 0xff : 0, hb, m.stream));
@@ -792,11 +789,11 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
             fclose(f);
         }
         if (chain.empty() || chain[0] + 1 != chain.size() || (size_t)max_levels < 4 * chain.size()) {
-            (void)hipFree(dmem);
             set_error("hclib_hip_uts_search: chain trace needs HCLIB_HIP_UTS_CHAIN and max_levels >= 4 (D + 1)");
             return HCLIB_HIP_EINVAL;
         }
-        HX_HIP(hipMalloc(&d_chain, chain.size() * 4));
+        HX_TRY(chain_buf.alloc(chain.size() * 4, "hclib_hip_uts_search"));
+        d_chain = (uint32_t *)chain_buf.p;
         HX_HIP(hipMemcpy(d_chain, chain.data(), chain.size() * 4, hipMemcpyHostToDevice));
     }
 
@@ -898,14 +895,9 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     const int grid = env_int("HCLIB_HIP_GRID", 0) > 0
                          ? env_int("HCLIB_HIP_GRID", 0)
                          : m.num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", wpc_default);
-    // a knob value that cannot fit the ring is refused here, before the
-    // launch (as check_resident refuses a grid that cannot be resident),
-    // instead of ending in a device error after it
-    auto refuse = [&]() {
-        if (dmem) (void)hipFree(dmem);
-        if (d_chain) (void)hipFree(d_chain);
-        return HCLIB_HIP_EINVAL;
-    };
+    // (a knob value that cannot fit the ring is refused below, before the
+    // launch, as check_resident refuses a grid that cannot be resident,
+    // instead of ending in a device error after it)
     if (bin_seed) {
         // the seeding's fit test, as the fixed-shape one below: level d holds
         // the slots of depth d + 1, expected n(1) = the root's children and
@@ -940,7 +932,7 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     if (ring_used != 256 && ring_used != 512 && ring_used != 1024) {
         set_error("hclib_hip_uts_search: HCLIB_HIP_UTS_RING=%d is not a ring the search is built for (256, 512 or 1024 "
                   "items per wave)", ring_used);
-        return refuse();
+        return HCLIB_HIP_EINVAL;
     }
     // BIN trees: 66 since the register carry went through LDS (T3L 30.64 ->
     // 30.20 ms same-box against 72, profiles/r04/sc_ab_t3l*.log, t3l3_spill.log);
@@ -970,13 +962,13 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
             if (per_wave < 1) {
                 set_error("hclib_hip_uts_search: HCLIB_HIP_SEED_PER_WAVE=%d is not a slot count (1 or more; "
                           "HCLIB_HIP_UTS_SEED=0 turns the seeding off)", per_wave);
-                return refuse();
+                return HCLIB_HIP_EINVAL;
             }
             if (b * per_wave > ring_used / 2) {
                 set_error("hclib_hip_uts_search: HCLIB_HIP_SEED_PER_WAVE=%d cannot fit the ring: a wave's share of the "
                           "seeded level reaches %.0f x %d items, the seeding hands over at most %d of a %d-item ring",
                           per_wave, b, per_wave, ring_used / 2, ring_used);
-                return refuse();
+                return HCLIB_HIP_EINVAL;
             }
         }
         // ... and the launch is seeded only where that level fits, by the
@@ -1006,7 +998,7 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
         if (lo < 1 || lo > ring_launch) {
             set_error("hclib_hip_uts_search: HCLIB_HIP_SPILL_LO=%d does not fit the %d-item ring of this launch "
                       "(1..%d)", lo, ring_launch, ring_launch);
-            return refuse();
+            return HCLIB_HIP_EINVAL;
         }
     }
     cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_SPILL_LO", spill_lo_default);
@@ -1099,8 +1091,6 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     uts_kernel_t kern = kernels[mode][feat ? 1 : 0];
     if (trace) {
         if (mode != kUtsBin || nshards > 1) {
-            (void)hipFree(dmem);
-            if (d_chain) (void)hipFree(d_chain);
             set_error("hclib_hip_uts_search: the depth trace is for unsharded BIN trees");
             return HCLIB_HIP_EINVAL;
         }
@@ -1153,8 +1143,6 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
         HX_HIP(hipMemcpy(h.data(), d_hist, hb, hipMemcpyDeviceToHost));
         for (int i = 0; i < max_levels; ++i) level_hist[i] = h[i];
     }
-    (void)hipFree(dmem);
-    if (d_chain) (void)hipFree(d_chain);
     if (rc != HCLIB_HIP_OK) return rc;
     result->nodes = gl.counters[0];
     result->leaves = gl.counters[1];

@@ -85,7 +85,16 @@ extern "C" {
 /* hclib_hip_init: bind the calling process to HIP device `device` (the
  * module's post-init hook, inc/hclib-module.h:62-64). Idempotent. */
 int hclib_hip_init(int device);
+/* hclib_hip_finalize: wait for the module stream and free every device
+ * allocation the library holds on its own account; hclib_hip_init (of any
+ * device) starts again from nothing. Handles the caller owns (atomics, SW band
+ * sessions, global regions, locale allocations, forasync op records) stay the
+ * caller's to release. */
 void hclib_hip_finalize(void);
+/* out[0] = live device allocations, out[1] = their bytes, of the library's own
+ * account (its arenas and per-call buffers; not the caller-owned handles
+ * above): {0, 0} after hclib_hip_finalize */
+void hclib_hip_device_memory_live(uint64_t out[2]);
 const char *hclib_hip_last_error(void);
 /* Number of CUs / XCDs of the bound device (0 if none). */
 int hclib_hip_num_cus(void);
