@@ -140,7 +140,7 @@ EXPORTS_HIP = [
     "hclib_hip_num_workers", "hclib_hip_uts_search", "hclib_hip_uts_num_children_host",
     "hclib_hip_uts_bucket_check", "hclib_hip_sha1_calibrate",
     "hclib_hip_fib", "hclib_hip_sw", "hclib_hip_last_sched_counters", "hclib_hip_last_narrow_counters",
-    "hclib_hip_last_phase_counters",
+    "hclib_hip_last_phase_counters", "hclib_hip_last_shed_counters",
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
@@ -865,6 +865,14 @@ def last_narrow_counters():
     out = (C.c_uint64 * 4)()
     lib().hclib_hip_last_narrow_counters(out)
     return list(out)
+
+
+def last_shed_counters():
+    """The narrow loop's overflow exits of the last launch
+    (hclib_hip_last_shed_counters): exits, placed, blocks, items, fallbacks."""
+    out = (C.c_uint64 * 8)()
+    lib().hclib_hip_last_shed_counters(out)
+    return dict(zip(("exits", "placed", "blocks", "items", "fallbacks"), out))
 
 
 TIMELINE_EVENTS = {1: "start", 2: "busy", 3: "idle", 4: "spill", 5: "term", 6: "end"}

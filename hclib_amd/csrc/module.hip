@@ -279,6 +279,7 @@ int finish_sched(SchedGlobals *host_copy, const char *who) {
         for (int i = 0; i < 4; ++i)
             if (r[16 + i] > host_copy->maxes[i]) host_copy->maxes[i] = r[16 + i];
         for (int i = 0; i < 3; ++i) host_copy->narrow[i] += r[20 + i];
+        for (int i = 0; i < kShedCounts; ++i) host_copy->shed[i] += r[32 + i];
         m.last_phase[0] += r[23];
         for (int i = 0; i < 4; ++i) m.last_phase[1 + i] += r[28 + i];
         m.last_phase[5] += r[24];  // HX_PHASES builds only (else the stamps' push cycles)
@@ -286,6 +287,7 @@ int finish_sched(SchedGlobals *host_copy, const char *who) {
     }
     memcpy(m.last_counters, host_copy->counters, sizeof(m.last_counters));
     memcpy(m.last_narrow, host_copy->narrow, sizeof(m.last_narrow));
+    memcpy(m.last_shed, host_copy->shed, sizeof(m.last_shed));
     // every wave of the grid leaves exactly once: counters[kCtrWaves] records
     uint64_t nw = host_copy->counters[kCtrWaves];
     if (nw > nw_cap) nw = nw_cap;
@@ -385,6 +387,10 @@ extern "C" void hclib_hip_last_phase_counters(uint64_t out[8]) {
 
 void hclib_hip_last_narrow_counters(uint64_t out[4]) {
     for (int i = 0; i < 4; ++i) out[i] = g_mod.last_narrow[i];
+}
+
+void hclib_hip_last_shed_counters(uint64_t out[8]) {
+    for (int i = 0; i < 8; ++i) out[i] = g_mod.last_shed[i];
 }
 
 int hclib_hip_last_wave_stats(hclib_hip_wave_stats_t *out, int max) {

@@ -1030,6 +1030,21 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     // 512-item rings)
     cfg.dual = (uint32_t)env_int("HCLIB_HIP_UTS_DUAL", 1);
     cfg.spills = (uint32_t)env_int("HCLIB_HIP_SPILLS_PER_BATCH", 0);
+    // the narrow loop's overflow exit (hx_sched.h narrow_shed; BIN trees in
+    // workgroups of 2 or 4 waves): HCLIB_HIP_NARROW_SHED = 0 every child onto
+    // the ring and back to the main loop, 1 keep half the level's spawners and
+    // hand the others' children to idle siblings, 2 keep as many as fit one
+    // batch, 3 keep a quarter; HCLIB_HIP_NARROW_SHED_SIBS = the sibling
+    // inboxes one exit may fill (0: none, every exit falls back to the ring)
+    {
+        const int rule = env_int("HCLIB_HIP_NARROW_SHED", 1), sibs = env_int("HCLIB_HIP_NARROW_SHED_SIBS", 3);
+        if (rule < 0 || rule > 3 || sibs < 0 || sibs > 3) {
+            set_error("hclib_hip_uts_search: HCLIB_HIP_NARROW_SHED=%d / HCLIB_HIP_NARROW_SHED_SIBS=%d: the keep rule is "
+                      "0 (off), 1, 2 or 3, the sibling inboxes per exit 0..3", rule, sibs);
+            return HCLIB_HIP_EINVAL;
+        }
+        cfg.narrow_shed = (uint32_t)rule | (uint32_t)sibs << 8;
+    }
     // breadth-first seeding (hx_sched.h seed_levels) for fixed-shape GEO
     // trees: the grid expands the top levels together and shares the level
     // that reaches HCLIB_HIP_SEED_PER_WAVE slots per wave out evenly, instead

@@ -130,6 +130,12 @@ int hclib_hip_last_wave_stats(hclib_hip_wave_stats_t *out, int max);
 /* The narrow-frontier carry loop of the last launch (hx_sched.h): [0]
  * batches run in it, [1] shader-clock cycles spent in it, [2] entries. */
 void hclib_hip_last_narrow_counters(uint64_t out[4]);
+/* That loop's overflow exits in workgroups with sibling waves (a level that
+ * outgrew one batch; hx_sched.h narrow_shed; zeros with HCLIB_HIP_NARROW_SHED=0):
+ * [0] exits, [1] exits whose shed children all went to idle siblings' LDS
+ * inboxes (the loop went on), [2] inboxes filled, [3] items in them, [4]
+ * exits that left children for the ring and the main loop; [0] = [1] + [4]. */
+void hclib_hip_last_shed_counters(uint64_t out[8]);
 /* Diagnostic (HX_PHASES builds, zeros otherwise): [0] main-loop single
  * batches of the last megakernel launch, [1..4] their s_memtime cycles from
  * loop top to pop issued, pop landed, body done, batch end. */

@@ -158,6 +158,7 @@ struct alignas(256) SchedGlobals {
         uint32_t min_levels;   // ... but not before this many (a sharded search: past its split)
         uint32_t solo_cap;     // wave 0 runs levels of at most this many slots alone (0: the ring's room)
     } seed;
+    unsigned long long shed[8];  // narrow-loop overflow sheds (kShed* below), summed over the waves
 };
 constexpr int kSeedMaxLevels = 24;
 constexpr int kSeedGoLines = 64;  // "level d is complete" broadcast lines (a wave polls line gid % 64)
@@ -165,8 +166,18 @@ constexpr int kSeedCtlLines = 2 * kSeedMaxLevels + 2 + kSeedGoLines;
 // a worker's exit record: [0..7] the kind's counters, [8..15] the
 // scheduler's counters (SchedGlobals::counters [8..15]; [4..7] of the
 // diagnostic stamps go to [24..27]), [16..19] the kind's maxima, [20..22]
-// the narrow-loop counts
-constexpr int kWaveCtrWords = 32;
+// the narrow-loop counts, [32..36] the narrow-loop overflow sheds (kShed*)
+constexpr int kWaveCtrWords = 40;
+// narrow-loop overflow exits of a wave with siblings (narrow_shed; all 0 with
+// SchedConfig::narrow_shed off): every exit is either placed or a fallback
+enum : int {
+    kShedExits = 0,      // overflow exits that tried to shed
+    kShedPlaced = 1,     // ... whose shed spawners all went to siblings (the loop went on)
+    kShedBlocks = 2,     // inboxes filled
+    kShedItems = 3,      // items in them
+    kShedFallbacks = 4,  // exits with spawners left over (onto the ring, back to the main loop)
+    kShedCounts = 5,
+};
 
 // Diagnostic build (-DHX_TIMELINE=1, `python -m hclib_amd.build --variant
 // timeline`): every worker logs its transitions — start, busy (work taken),
@@ -266,6 +277,12 @@ struct SchedConfig {
     // shares, from spill_lo items), 1 = they see none hungry (every wave holds
     // its share)
     uint32_t hunger_init_full = 0;
+    // the fixed-size narrow loop's overflow exit in a workgroup with siblings
+    // (narrow_shed; read only there). Bits 0..7: 0 = every child onto the ring
+    // and back to the main loop; else the spawners the wave keeps as its next
+    // level: 1 = half, 2 = as many as fit one batch, 3 = a quarter (each
+    // capped at one batch). Bits 8..15: sibling inboxes one exit may fill
+    uint32_t narrow_shed = 0;
 };
 
 // Kind concept:
@@ -375,11 +392,26 @@ struct KindFixedChildren<K, decltype((void)K::kFixedChildren)> {
 };
 constexpr uint32_t kMaxChildren = 1u << 24;  // kend shares its descriptor word with delta
 
+// what the narrow loop's overflow exit (narrow_shed) needs of its
+// surroundings, parked in LDS (run_worker stores it once) so that none of it
+// rides along the loop's levels in registers, and that exit's counts
+// (kShed*); on the rings that have the carry slots (WaveStack::kCarryLds)
+template <bool ON>
+struct ShedSlots {};
+template <>
+struct ShedSlots<true> {
+    unsigned long long shed_g;  // SchedGlobals *
+    uint32_t shed_ib;           // LDS address of the workgroup's inboxes
+    uint32_t shed_wave;         // this wave's index among them
+    uint32_t shed_cfg;          // SchedConfig::narrow_shed
+    uint32_t shed_cnt[kShedCounts];
+};
+
 // register carry through LDS (carry_lds) where the ring's stack has room,
 // carry_permute elsewhere (through LDS: T3L 31.29 -> 30.59 ms,
 // profiles/r04/carry_ab_t3l.log)
 template <class Kind, int CAP>
-struct WaveStack {
+struct WaveStack : ShedSlots<(CAP >= 1024)> {
     static constexpr int TW = Kind::kTmplWords;
     static_assert(TW == 2 || TW == 6, "templates are 2 or 6 words");
     static_assert((CAP & (CAP - 1)) == 0, "CAP must be a power of two");
@@ -945,18 +977,7 @@ __device__ __forceinline__ void carry_permute(unsigned long long spawn, uint32_t
 // (`mine`: this lane's bit of `spawn`, when the caller has it as a lane mask
 // already — testing the bit again is three VALU instructions per carry)
 template <int TW>
-__device__ __forceinline__ void carry_lds_slot(uint4 *scr, unsigned long long spawn, bool mine, const uint32_t *child,
-                                               uint32_t *ctmpl, uint32_t r) {
-    const uint32_t rk = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(spawn >> 32),
-                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)spawn, 0u));
-    if (mine) {
-        if constexpr (TW == 6) {
-            scr[2 * rk] = make_uint4(child[0], child[1], child[2], child[3]);
-            *(uint2 *)&scr[2 * rk + 1] = make_uint2(child[4], child[5]);
-        } else {
-            *(uint2 *)&scr[2 * rk] = make_uint2(child[0], child[1]);
-        }
-    }
+__device__ __forceinline__ void carry_lds_read(const uint4 *scr, uint32_t r, uint32_t *ctmpl) {
     if constexpr (TW == 6) {
         const uint4 a = scr[2 * r];
         const uint2 b = *(const uint2 *)&scr[2 * r + 1];
@@ -971,6 +992,21 @@ __device__ __forceinline__ void carry_lds_slot(uint4 *scr, unsigned long long sp
         ctmpl[0] = a.x;
         ctmpl[1] = a.y;
     }
+}
+template <int TW>
+__device__ __forceinline__ void carry_lds_slot(uint4 *scr, unsigned long long spawn, bool mine, const uint32_t *child,
+                                               uint32_t *ctmpl, uint32_t r) {
+    const uint32_t rk = (uint32_t)__builtin_amdgcn_mbcnt_hi((uint32_t)(spawn >> 32),
+                                                           __builtin_amdgcn_mbcnt_lo((uint32_t)spawn, 0u));
+    if (mine) {
+        if constexpr (TW == 6) {
+            scr[2 * rk] = make_uint4(child[0], child[1], child[2], child[3]);
+            *(uint2 *)&scr[2 * rk + 1] = make_uint2(child[4], child[5]);
+        } else {
+            *(uint2 *)&scr[2 * rk] = make_uint2(child[0], child[1]);
+        }
+    }
+    carry_lds_read<TW>(scr, r, ctmpl);
 }
 
 template <int TW>
@@ -1139,7 +1175,16 @@ __device__ __forceinline__ void acc_set_wid(A &a, uint32_t w) {
 // kept as two scalar sums (the carry and t2) instead of per-lane adds, and no
 // uniformity branches. The general loop below compiled this case to ~70
 // instructions around the SHA-1 with five taken branches per level.
-template <class Kind, int CAP>
+// A level that outgrows one batch (t2 > 64) in a workgroup with siblings
+// (WPG > 1) first tries narrow_shed (below the inboxes): the wave keeps some
+// spawners' children as its next level and hands the others' to idle
+// siblings, and the loop goes on. Spawners it could not place go onto the
+// ring as before, behind the kept ones in the carry.
+template <class Kind, int CAP, int WPG>
+__device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, WaveStack<Kind, CAP> &st, uint32_t mu,
+                                                uint32_t nsp, uint32_t r_fix, uint32_t ck_fix, uint32_t &to_ring);
+
+template <class Kind, int CAP, int WPG = 1>
 __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop_fixed(
     const typename Kind::Ctx &ctx_ref, typename Kind::Acc &acc_ref, uint32_t *err, WaveStack<Kind, CAP> &st,
     NarrowState<Kind::kTmplWords> ns, uint32_t mu, uint32_t r_fix, uint32_t ck_fix) {
@@ -1162,6 +1207,7 @@ __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop_fixed(
     // one exit test per level (t2 = 0: nothing spawned; t2 > one batch: onto
     // the ring below): a chain level spawns and carries and falls through
     // to the back-edge
+    while (true) {
     do {
         const bool h = lane < carry;
         if constexpr (kBulk) sp = Kind::process_bulk(ctx, acc, ns.ctmpl, k, ch2, err, h);
@@ -1180,15 +1226,23 @@ __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop_fixed(
         carry_lds_slot<TW>(st.cscr, sp2, sp, ch2, ns.ctmpl, r_fix);
         carry = t2;
     } while (t2 - 1u < (uint32_t)kWaveSize);
-    ns.ck = ck_fix;
-    if (t2 != 0) {
-        // more than one batch: onto the empty ring
-        const uint32_t rk2 = (uint32_t)__builtin_amdgcn_mbcnt_hi(
-            (uint32_t)(sp2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sp2, 0u));
-        push_uniform<Kind, CAP>(st, ns.top, mu * rk2, t2, mu, sp, ch2);
-        ns.top += t2;
-        carry = 0;
+    if (t2 == 0) break;
+    // more than one batch. With siblings: the first `kept` spawners' children
+    // stay (the carry just read them into lanes < mu * kept), those of ranks
+    // kept..to_ring-1 went to siblings; the others' go onto the empty ring
+    // (kept = 0: all of them, the exit of a workgroup of one wave)
+    const uint32_t nsp = (uint32_t)__builtin_popcountll(sp2);
+    uint32_t kept = 0, to_ring = 0;
+    if constexpr (WPG > 1) kept = narrow_shed<Kind, CAP, WPG>(ctx, st, mu, nsp, r_fix, ck_fix, to_ring);
+    carry = mu * kept;
+    if (kept != 0 && to_ring == nsp) continue;
+    const uint32_t rk2 = (uint32_t)__builtin_amdgcn_mbcnt_hi(
+        (uint32_t)(sp2 >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)sp2, 0u));
+    push_uniform<Kind, CAP>(st, ns.top, mu * (rk2 - to_ring), mu * (nsp - to_ring), mu, sp && rk2 >= to_ring, ch2);
+    ns.top += mu * (nsp - to_ring);
+    break;
     }
+    ns.ck = ck_fix;
     if constexpr (kBulk) Kind::count_bulk(acc, s_exec, s_exec - s_nsp);
     if (lane == 0) {
         ns.n_exec += s_exec;
@@ -1201,7 +1255,7 @@ __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop_fixed(
     return ns;
 }
 
-template <class Kind, int CAP>
+template <class Kind, int CAP, int WPG = 1>
 __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop(
     const typename Kind::Ctx &ctx_ref, typename Kind::Acc &acc_ref, uint32_t *err, WaveStack<Kind, CAP> &st,
     NarrowState<Kind::kTmplWords> ns) {
@@ -1228,7 +1282,7 @@ __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop(
     const uint32_t ck_fix = hoist ? lane - __umul24(r_fix, mu_fix) : 0u;
     if constexpr (KindFixedChildren<Kind>::value && Kind::kPure && Kind::kBoundedChildren &&
                   WaveStack<Kind, CAP>::kCarryLds) {
-        if (hoist) return narrow_loop_fixed<Kind, CAP>(ctx_ref, acc_ref, err, st, ns, mu_fix, r_fix, ck_fix);
+        if (hoist) return narrow_loop_fixed<Kind, CAP, WPG>(ctx_ref, acc_ref, err, st, ns, mu_fix, r_fix, ck_fix);
     }
     while (true) {
         const bool h = lane < carry;
@@ -1322,6 +1376,39 @@ struct Inbox {
     uint32_t w[64 * Kind::kWords];
 };
 
+// lane 0's claim of an empty inbox (LDS CAS 0 -> 2; the caller broadcasts it
+// once the reads it issues beside the claim are out)
+template <class Kind>
+__device__ __forceinline__ uint32_t inbox_claim(Inbox<Kind> &ib) {
+    uint32_t ok = 0;
+    if (lane_id() == 0) ok = lds_cas(&ib.state, 0u, 2u) ? 1u : 0u;
+    return ok;
+}
+
+// fill a claimed inbox with the wave's n items (lane i < n holds item i as
+// w = {template, k, kend}) and set it full: the items, the chunk's unit of
+// `outstanding`, then n, idle = 0 and the state, in that order
+template <class Kind>
+__device__ __forceinline__ void inbox_fill(const typename Kind::Ctx &ctx, Inbox<Kind> &ib, uint32_t *w, bool valid,
+                                           uint32_t n, SchedGlobals *g) {
+    constexpr int W = Kind::kWords;
+    kind_export<Kind>(ctx, w, valid, &g->err);
+    kind_trace_item<Kind>(ctx, w, valid, 2u, true);
+    if (valid) {
+        // (address-space-3 stores: DS operations, in order with the flags' below)
+        hx_lds_u32 *dst = (hx_lds_u32 *)&ib.w[(uint32_t)lane_id() * W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) dst[i] = w[i];
+    }
+    asm volatile("" ::: "memory");
+    if (lane_id() == 0) {
+        add_agent(&g->outstanding, 1u);  // the chunk's unit, before it becomes visible
+        lds_store(&ib.n, n);
+        lds_store(&ib.idle, 0u);
+        lds_store(&ib.state, 1u);  // after the items (one wave's DS operations land in order)
+    }
+}
+
 template <class Kind, int CAP>
 __device__ bool inbox_put(const typename Kind::Ctx &ctx, Inbox<Kind> &ib, WaveStack<Kind, CAP> &st, uint32_t bot,
                           uint32_t n, SchedGlobals *g) {
@@ -1332,29 +1419,80 @@ __device__ bool inbox_put(const typename Kind::Ctx &ctx, Inbox<Kind> &ib, WaveSt
     const bool valid = (uint32_t)lane < n;
     const uint32_t p = bot + (valid ? (uint32_t)lane : 0u);
     const uint2 dd = st.d[p & (CAP - 1)];
-    uint32_t ok = 0;
-    if (lane == 0) ok = lds_cas(&ib.state, 0u, 2u) ? 1u : 0u;
+    const uint32_t ok = inbox_claim<Kind>(ib);
     uint32_t w[W];
     load_tmpl<Kind, CAP>(st, (p - (dd.y >> 24)) & (CAP - 1), w);
     if (!lane0(ok)) return false;
-    {
-        w[W - 2] = dd.x;
-        w[W - 1] = dd.y & (kMaxChildren - 1);
-        kind_export<Kind>(ctx, w, valid, &g->err);
-        kind_trace_item<Kind>(ctx, w, valid, 2u, true);
-        if (valid) {
+    w[W - 2] = dd.x;
+    w[W - 1] = dd.y & (kMaxChildren - 1);
+    inbox_fill<Kind>(ctx, ib, w, valid, n, g);
+    return true;
+}
+
+// The narrow loop's overflow exit (narrow_loop_fixed, WPG > 1). The level's
+// nsp spawners (mu children each, more than one batch together) have their
+// templates in st.cscr slots 0..nsp-1 and the ring is empty. The wave keeps
+// the first `keep` spawners (their children are already in lanes
+// < mu * keep: nothing moves) and writes the children of the others, in
+// blocks of whole spawners of at most one batch, from the carry slots
+// straight into the inboxes of idle siblings: no ring traffic and no return
+// to the main loop between two levels of the chain. Returns keep (0: shedding
+// is off) and in `to_ring` the first spawner rank it could not place (nsp:
+// none left). Every sibling's flags are read in one go, as run_worker's
+// give-away does.
+template <class Kind, int CAP, int WPG>
+__device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, WaveStack<Kind, CAP> &st, uint32_t mu,
+                                                uint32_t nsp, uint32_t r_fix, uint32_t ck_fix, uint32_t &to_ring) {
+    constexpr int TW = Kind::kTmplWords, W = Kind::kWords;
+    const uint32_t lane = (uint32_t)lane_id();
+    to_ring = 0;
+    const uint32_t cfg = lane0(lds_load(&st.shed_cfg));
+    const uint32_t rule = cfg & 0xffu, max_blocks = (cfg >> 8) & 0xffu;
+    if (rule == 0) return 0;
+    const uint32_t fit = (64u * rcp16(mu)) >> 16;  // spawners whose children are one batch (64 / mu)
+    uint32_t keep = rule == 2 ? fit : (rule == 3 ? nsp / 4 : nsp / 2);
+    keep = keep > fit ? fit : (keep == 0 ? 1u : keep);
+    const uint32_t wave = lane0(lds_load(&st.shed_wave));
+    typedef __attribute__((address_space(3))) Inbox<Kind> lds_inbox;
+    Inbox<Kind> *ib = (Inbox<Kind> *)(lds_inbox *)(uintptr_t)lane0(lds_load(&st.shed_ib));
+    const unsigned long long gp = st.shed_g;
+    SchedGlobals *g = (SchedGlobals *)(((unsigned long long)lane0((uint32_t)(gp >> 32)) << 32) | lane0((uint32_t)gp));
+    uint32_t sid[WPG], sst[WPG];
 #pragma unroll
-            for (int i = 0; i < W; ++i) ib.w[(uint32_t)lane * W + i] = w[i];
+    for (uint32_t a = 1; a < (uint32_t)WPG; ++a) {
+        sid[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].idle);
+        sst[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].state);
+    }
+    const uint32_t nshed = nsp - keep;  // > 0: nsp > fit >= keep
+    uint32_t placed = 0, blocks = 0;
+#pragma unroll
+    for (uint32_t a = 1; a < (uint32_t)WPG; ++a) {
+        if (placed < nshed && blocks < max_blocks && lane0(sid[a]) == 1u && lane0(sst[a]) == 0u) {
+            Inbox<Kind> &to = ib[(wave + a) % (uint32_t)WPG];
+            const uint32_t bs = nshed - placed < fit ? nshed - placed : fit, n = bs * mu;
+            const bool valid = lane < n;
+            // item o of the block is child o % mu of spawner keep + placed + o / mu
+            // (its slot's read goes out beside the claim)
+            const uint32_t ok = inbox_claim<Kind>(to);
+            uint32_t w[W];
+            carry_lds_read<TW>(st.cscr, keep + placed + (valid ? r_fix : 0u), w);
+            if (lane0(ok)) {
+                w[W - 2] = ck_fix;
+                w[W - 1] = ck_fix + 1u;
+                inbox_fill<Kind>(ctx, to, w, valid, n, g);
+                placed += bs;
+                ++blocks;
+            }
         }
     }
-    asm volatile("" ::: "memory");
+    to_ring = keep + placed;
     if (lane == 0) {
-        add_agent(&g->outstanding, 1u);  // the chunk's unit, before it becomes visible
-        lds_store(&ib.n, n);
-        lds_store(&ib.idle, 0u);
-        lds_store(&ib.state, 1u);  // after the items (one wave's DS operations land in order)
+        st.shed_cnt[kShedExits] += 1u;
+        st.shed_cnt[placed == nshed ? kShedPlaced : kShedFallbacks] += 1u;
+        st.shed_cnt[kShedBlocks] += blocks;
+        st.shed_cnt[kShedItems] += placed * mu;
     }
-    return true;
+    return keep;
 }
 
 // take a full inbox into the (empty) ring; returns the items (0: empty)
@@ -1725,6 +1863,16 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
     uint32_t tag = 1;  // mark tags: 16 per batch
     for (int i = lane; i < kWaveSize; i += kWaveSize) st.mark[i] = 0;
     if (lane < 8) st.stolen_from[lane] = 0;
+    constexpr bool kShed = WPG > 1 && WaveStack<Kind, CAP>::kCarryLds;  // narrow_shed can run
+    if constexpr (kShed) {
+        if (lane == 0) {
+            st.shed_g = (unsigned long long)(uintptr_t)g;
+            st.shed_ib = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) Inbox<Kind> *)ib;
+            st.shed_wave = wave;
+            st.shed_cfg = cfg.narrow_shed;
+        }
+        if (lane < kShedCounts) st.shed_cnt[lane] = 0;
+    }
     uint32_t n_exec = 0, n_spawn = 0;          // per lane: tasks run, children created
     uint32_t items_stolen = 0;
     uint32_t n_narrow = 0, n_narrow_in = 0;
@@ -2225,7 +2373,7 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
                     ns.n_exec = n_exec;
                     ns.n_spawn = n_spawn;
                     ns.batches = 0;
-                    ns = narrow_loop<Kind, CAP>(ctx, acc, &g->err, st, ns);
+                    ns = narrow_loop<Kind, CAP, WPG>(ctx, acc, &g->err, st, ns);
 #pragma unroll
                     for (int i = 0; i < TW; ++i) ctmpl[i] = ns.ctmpl[i];
                     ck = ns.ck;
@@ -2339,6 +2487,11 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
     __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0): the LDS sums have landed
     const unsigned long long cyc_busy = st.cyc[0], cyc_idle = st.cyc[1], cyc_spill = st.cyc[2],
                              cyc_narrow = st.cyc[3], t_begin = st.cyc[4], rt_begin = st.cyc[5];
+    // lanes 32.. hold the narrow loop's shed counts (exit record words 32..)
+    unsigned long long shed_v = 0;
+    if constexpr (kShed) {
+        if (lane >= 32 && lane < 32 + kShedCounts) shed_v = st.shed_cnt[lane - 32];
+    }
     if (active) {
         // only reached on an error break: keep the protocol consistent
         wave_goes_idle<GLOBAL>(g, gv, pool);
@@ -2381,7 +2534,7 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
                              c_proc = (HX_STAMPS && cfg.stamps) ? cyc_proc : 0;
     if (rec) {
         // one store instruction: lane i writes word i of the record
-        unsigned long long v = 0;
+        unsigned long long v = shed_v;
 #pragma unroll
         for (int i = 0; i < 8; ++i)
             if (lane == i) v = kc[i];
@@ -2413,6 +2566,7 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
         }
         if (lane < kWaveCtrWords) g->wave_ctr[(size_t)gid * kWaveCtrWords + lane] = v;
     } else {
+        if (shed_v) add_agent(&g->shed[lane - 32], shed_v);
         if (lane == 0 && n_narrow_in) {
             add_agent(&g->narrow[0], (unsigned long long)n_narrow);
             add_agent(&g->narrow[1], cyc_narrow);
