@@ -125,6 +125,29 @@ class StrassenResult(C.Structure):
                 ("kernel_ms", C.c_double), ("gflops", C.c_double)]
 
 
+class HealthParams(C.Structure):
+    """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
+
+    _fields_ = [(k, C.c_int) for k in ("level", "cities", "population_ratio", "sim_time", "assess_time",
+                                       "convalescence_time")] + [("seed", C.c_int32)] + \
+               [(k, C.c_float) for k in ("get_sick_p", "convalescence_p", "realloc_p")]
+
+
+class HealthResult(C.Structure):
+    """hclib_hip_health_result_t."""
+
+    _fields_ = [(k, C.c_int64) for k in ("population", "hospitals", "personnel", "hosps_visited", "in_village",
+                                         "waiting", "assess", "inside", "total_time")] + \
+               [(k, C.c_uint64) for k in ("tasks", "finishes", "check_ins", "leaf_calls", "inner_calls", "posts")] + \
+               [("kernel_ms", C.c_double), ("rounds_per_s", C.c_double)]
+
+
+class HealthState(C.Structure):
+    """hclib_hip_health_state_t."""
+
+    _fields_ = [(k, C.c_void_p) for k in ("seed", "time", "time_left", "hosps_visited", "village", "lists")]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -148,6 +171,7 @@ EXPORTS_HIP = [
     "hclib_hip_sparselu_genmat", "hclib_hip_sparselu_plan", "hclib_hip_sparselu", "hclib_hip_sparselu_bmod_rate",
     "hclib_hip_nqueens", "hclib_hip_nqueens_bounds",
     "hclib_hip_strassen", "hclib_hip_strassen_bounds", "hclib_hip_strassen_last_ticks",
+    "hclib_hip_health", "hclib_hip_health_bounds", "hclib_hip_health_last_ticks",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -233,6 +257,10 @@ def lib():
         L.hclib_hip_strassen_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.hclib_hip_strassen_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
         L.hclib_hip_strassen_last_ticks.restype = None
+        L.hclib_hip_health.argtypes = [C.POINTER(HealthParams), C.POINTER(HealthResult), C.POINTER(HealthState)]
+        L.hclib_hip_health_bounds.argtypes = [C.POINTER(HealthParams), C.POINTER(C.c_uint64)]
+        L.hclib_hip_health_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_health_last_ticks.restype = None
         _lib = L
     return _lib
 
@@ -821,6 +849,90 @@ def strassen_last_ticks() -> dict:
     out = (C.c_uint64 * 6)()
     lib().hclib_hip_strassen_last_ticks(out)
     return dict(zip(("multiply", "pre", "combine", "split", "fork", "post"), out))
+
+
+# --------------------------------------------------------------- BOTS Health
+HEALTH_PARAMS = tuple(k for k, _ in HealthParams._fields_)
+HEALTH_TOTALS = ("population", "hospitals", "personnel", "hosps_visited", "in_village", "waiting", "assess", "inside",
+                 "total_time")
+HEALTH_LISTS = ("population", "waiting", "assess", "inside")
+
+
+def _health_params(params) -> HealthParams:
+    if isinstance(params, HealthParams):
+        return params
+    if not isinstance(params, dict):
+        params = dict(zip(HEALTH_PARAMS, params))
+    if sorted(params) != sorted(HEALTH_PARAMS):
+        raise ValueError(f"health: params must give exactly {HEALTH_PARAMS}")
+    p = HealthParams()
+    for k in HEALTH_PARAMS[:6]:
+        setattr(p, k, int(params[k]))
+    s = int(params["seed"]) & 0xffffffff  # the low 32 bits of what the reference reads with %ld
+    p.seed = s - (1 << 32) if s & 0x80000000 else s
+    for k in HEALTH_PARAMS[7:]:
+        setattr(p, k, float(params[k]))
+    return p
+
+
+def health_read_input(path):
+    """A BOTS health input file (read_input_data, health.ref.c:487-535): 19
+    numbers, the ten settings and the nine expected results. Returns (params,
+    expected): params a dict for health(), expected the eight totals that
+    check_village compares, by health()'s names, and "avg_stay"."""
+    f = open(path).read().split()
+    if len(f) != 19:
+        raise ValueError(f"{path}: {len(f)} numbers, a health input file has 19")
+    params = dict(zip(HEALTH_PARAMS, [int(x) for x in f[:7]] + [float(x) for x in f[7:10]]))
+    expected = dict(zip(HEALTH_TOTALS[:8], (int(x) for x in f[10:18])))
+    expected["avg_stay"] = float(f[18])
+    return params, expected
+
+
+def health_bounds(params) -> dict:
+    """What a health() of these settings allocates (hclib_hip_health_bounds),
+    exact and on the host alone."""
+    out = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_health_bounds(C.byref(_health_params(params)), out), "hclib_hip_health_bounds")
+    return dict(zip(("villages", "patients", "tasks", "scopes", "wait_nodes", "arena_bytes"), out))
+
+
+def health(params, state: bool = False, expected=None) -> dict:
+    """BOTS Health on dynamic device dataflow (hclib_hip_health): sim_time
+    rounds over the village tree in one launch. params is a dict of
+    HEALTH_PARAMS (or the ten values in that order). Returns the fields of
+    hclib_hip_health_result_t; with state, "state": the reference's full final
+    state as numpy arrays (seed, time, time_left, hosps_visited per patient id;
+    village, one row of id, level, free_personnel and the four list lengths per
+    village in allocation order; lists, the lists' ids village by village); with
+    expected (health_read_input's), "verified": the reference's check_village
+    comparison of the eight totals."""
+    import numpy as np
+
+    p = _health_params(params)
+    st, arrays = None, None
+    if state:
+        b = health_bounds(p)
+        arrays = {k: np.zeros(b["patients"], dtype=np.int32) for k in ("seed", "time", "time_left", "hosps_visited",
+                                                                         "lists")}
+        arrays["village"] = np.zeros((b["villages"], 7), dtype=np.int32)
+        st = HealthState(**{k: a.ctypes.data for k, a in arrays.items()})
+    r = HealthResult()
+    _check(lib().hclib_hip_health(C.byref(p), C.byref(r), C.byref(st) if st is not None else None), "hclib_hip_health")
+    out = {k: getattr(r, k) for k, _ in HealthResult._fields_}
+    if state:
+        out["state"] = arrays
+    if expected is not None:
+        out["verified"] = all(out[k] == expected[k] for k in HEALTH_TOTALS[:8])
+    return out
+
+
+def health_last_ticks() -> dict:
+    """Wave time of the last health() by task class, in ticks of the 100 MHz
+    device clock (hclib_hip_health_last_ticks)."""
+    out = (C.c_uint64 * 3)()
+    lib().hclib_hip_health_last_ticks(out)
+    return dict(zip(("leaf_call", "inner_call", "post"), out))
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

@@ -1,7 +1,8 @@
 // hx_client.h — what the clients of the device dataflow runtimes share:
 // run_dag_group clients (cholesky.hip, sparselu.hip) the version graph, the
 // one-promise Kind and the launch; run_dyn_worker clients (sort.hip,
-// strassen.hip) the per-class counters, the timed Kind and the launch.
+// strassen.hip, health.hip) the per-class counters, the timed Kind and the
+// launch.
 #pragma once
 
 #include <string.h>

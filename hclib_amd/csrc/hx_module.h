@@ -31,6 +31,7 @@ enum ArenaId {
     kArenaSparselu,    // blocks and the slot table
     kArenaSort,        // class counters, the array and tmp
     kArenaStrassen,    // class counters, A, B, C and the temporaries
+    kArenaHealth,      // class counters, village tables, patient records and the lists' arena
     kArenaUtsTables,   // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };

@@ -52,6 +52,12 @@
  *                                    strassen.c, strassen.ref.c:580-788), the two
  *                                    sweeps as band tasks, as one launch of dynamic
  *                                    device dataflow
+ *   hclib_hip_health                 the task per village, the taskwait and the
+ *                                    sim_time loop of BOTS health (bots/health/
+ *                                    health.ref.c:426-461, 567-586; health.c:421-466)
+ *                                    with its five list walks as wave-wide
+ *                                    partitions, every round of the same fork-join
+ *                                    tree in one launch of dynamic device dataflow
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -772,6 +778,76 @@ int hclib_hip_strassen(const double *a, const double *b, double *c, int n,
                        int cutoff, int band_rows, hclib_hip_strassen_result_t *result);
 int hclib_hip_strassen_bounds(int n, int cutoff, int band_rows, uint64_t out[4]);
 void hclib_hip_strassen_last_ticks(uint64_t out[6]);
+
+/* -------------------------------------------------------------- Health */
+/* BOTS Health (test/performance-regression/full-apps/bots/health: health.ref.c
+ * the algorithm, health.c the HClib port) as ONE launch of dynamic device
+ * dataflow: sim_time rounds of sim_village_par over a tree of `level` levels
+ * with `cities` children per village. Every village is a task per round; one
+ * with children opens a finish scope for them, works on its own hospital while
+ * they run, and a continuation behind the scope takes in the patients they
+ * sent up, smallest id first (hclib_amd/csrc/health.hip has the task graph and
+ * the layout). The lists are arrays of patient ids, walked 64 at a time.
+ * params are the ten settings of a BOTS input file, in the file's order; seed
+ * is the low 32 bits of what the reference reads with %ld.
+ * The full final state is bit-identical to the reference's (any schedule, any
+ * compiler: every draw comes from the patient's own seed, and the reallocated
+ * patients are taken by id): my_rand on wrapping 32-bit words, its value one
+ * int -> float conversion and one f32 multiply by 2^-31.
+ * result: the nine sums of get_results (:197-276), sums of integers (the
+ * reference adds each time and each visit count as a float to a long: the same
+ * number while a sum is below 2^24); tasks, finishes and check_ins are what the
+ * device ran and equal the bounds: check_ins counts the tasks checked in to
+ * scopes, cities + 1 at every open. leaf_calls, inner_calls and posts are the
+ * tasks by class. rounds_per_s = sim_time / kernel time; the upload of the
+ * initial state and the download are outside kernel_ms.
+ * state (may be NULL) receives the final state into the caller's arrays:
+ * seed, time, time_left and hosps_visited, one word per patient, indexed by
+ * patient id (the reference's sim_pid order); village, seven words per village
+ * in the reference's allocation order (a village, then its children cities ..
+ * 1 with their subtrees): id, level, free_personnel, |population|, |waiting|,
+ * |assess|, |inside|; lists, one id per patient: village by village the four
+ * lists in that order, each in list order. Size them from the bounds.
+ * HCLIB_HIP_EINVAL before the device is touched: params or result NULL, a NULL
+ * array in state; level, cities or population_ratio < 1, sim_time < 0;
+ * assess_time or convalescence_time < 1 (a zero makes time_left step past zero
+ * and never return); a probability outside [0, 1] or NaN; cities * 2^(level-1)
+ * above 2048 (the most patients one village can receive in a round, which it
+ * sorts in LDS); level > 24, 2^31 or more villages or patients, 2^32 or more
+ * list words, or 2^32 - 16 or more tasks (sim_time * (villages + villages with
+ * children)), which 32-bit indices cannot address. sim_time = 0 is valid and
+ * returns the initial state without a launch. An arena the device cannot hold
+ * is HCLIB_HIP_ENOMEM.
+ * hclib_hip_health_bounds: host only, no GPU: out[0] villages, out[1]
+ * patients, out[2] tasks, out[3] finish scopes (promises), out[4] wait nodes,
+ * out[5] bytes of the arena (class counters, village tables, records, lists),
+ * all exact closed forms; the launch allocates exactly these. The same
+ * argument checks.
+ * hclib_hip_health_last_ticks: where the last launch's wave time went, ticks
+ * of the 100 MHz device clock summed over the tasks of each class, check-out
+ * included: [0] CALL of a village without children, [1] CALL of one with
+ * children, [2] POST. */
+typedef struct {
+    int level, cities, population_ratio, sim_time, assess_time, convalescence_time;
+    int32_t seed;
+    float get_sick_p, convalescence_p, realloc_p;
+} hclib_hip_health_params_t;
+typedef struct {
+    int64_t population, hospitals, personnel, hosps_visited, in_village, waiting, assess, inside, total_time;
+    uint64_t tasks, finishes, check_ins;
+    uint64_t leaf_calls, inner_calls, posts;
+    double kernel_ms;     /* device events around the one launch */
+    double rounds_per_s;
+} hclib_hip_health_result_t;
+typedef struct {
+    int32_t *seed, *time, *time_left, *hosps_visited; /* patients words each */
+    int32_t *village;                                 /* villages x 7 */
+    int32_t *lists;                                   /* patients words */
+} hclib_hip_health_state_t;
+int hclib_hip_health(const hclib_hip_health_params_t *params, hclib_hip_health_result_t *result,
+                     hclib_hip_health_state_t *state /* may be NULL */);
+int hclib_hip_health_bounds(const hclib_hip_health_params_t *params, uint64_t out[6]);
+void hclib_hip_health_last_ticks(uint64_t out[3]);
 
 #ifdef __cplusplus
 }
