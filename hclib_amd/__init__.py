@@ -82,6 +82,18 @@ class SwResult(C.Structure):
                 ("cells_per_s", C.c_double), ("tile_us", C.c_double), ("release_us", C.c_double)]
 
 
+class SwEdges(C.Structure):
+    """hclib_hip_sw_edges_t."""
+
+    _fields_ = [("bottoms", C.c_void_p), ("rights", C.c_void_p), ("corners", C.c_void_p),
+                ("path", C.c_int), ("form", C.c_int)]
+
+
+SW_EDGE_BOTTOMS, SW_EDGE_RIGHTS, SW_EDGE_CORNERS = 1, 2, 4
+# HCLIB_HIP_SW_PATH_*
+SW_PATHS = {1: "queue", 2: "rows1", 3: "band-rows", 4: "dag-wave", 5: "dag-wg", 6: "dag-pk"}
+
+
 class CholeskyResult(C.Structure):
     """hclib_hip_cholesky_result_t."""
 
@@ -165,6 +177,7 @@ EXPORTS_HIP = [
     "hclib_hip_fib", "hclib_hip_sw", "hclib_hip_last_sched_counters", "hclib_hip_last_narrow_counters",
     "hclib_hip_last_phase_counters", "hclib_hip_last_shed_counters",
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
+    "hclib_hip_sw_edges", "hclib_hip_sw_band_bottoms",
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
     "hclib_hip_atomic_gather", "hclib_hip_atomic_gather_async", "hclib_hip_atomic_reset",
     "hclib_hip_forasync_reduce", "hclib_hip_cholesky", "hclib_hip_sort_i64", "hclib_hip_sort_bounds",
@@ -212,6 +225,10 @@ def lib():
                                              C.c_void_p]
         L.hclib_hip_sw_band_end.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_int),
                                             C.POINTER(C.c_uint64)]
+        L.hclib_hip_sw_edges.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int,
+                                         C.c_int, C.POINTER(C.c_int), C.POINTER(SwResult),
+                                         C.POINTER(SwEdges), C.POINTER(C.c_uint32)]
+        L.hclib_hip_sw_band_bottoms.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.hclib_hip_atomic_calibrate.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_double),
                                                  C.POINTER(C.c_double)]
         L.hclib_hip_sha1_calibrate.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double),
@@ -526,6 +543,37 @@ def sw(s1: bytes, s2: bytes, tile_w: int, tile_h: int):
     return score.value, {k: getattr(r, k) for k, _ in SwResult._fields_}
 
 
+def sw_edges(s1: bytes, s2: bytes, tile_w: int, tile_h: int):
+    """sw(), plus what every tile put (hclib_hip_sw_edges): returns
+    (score, stats, edges). edges["bottoms"] is [nth][ntw*tw] (H of matrix
+    rows th, 2 th, ...), edges["rights"] [ntw][nth*th] (H of matrix columns
+    tw, 2 tw, ...), edges["corners"] [nth][ntw]: int32 arrays, or None where
+    the schedule that ran keeps no such array on the device. edges["path"]
+    names that schedule (SW_PATHS), edges["form"] its multi-wave band form."""
+    import numpy as np
+
+    ntw, nth = len(s1) // tile_w, len(s2) // tile_h
+    nt = max(ntw * nth, 0)
+    # poisoned: a value the read-back left alone cannot pass for a score
+    bottoms = np.full((nth, ntw * tile_w), -(1 << 30), dtype=np.int32)
+    rights = np.full((nt, tile_h), -(1 << 30), dtype=np.int32)
+    corners = np.full((nth, ntw), -(1 << 30), dtype=np.int32)
+    e = SwEdges(bottoms.ctypes.data, rights.ctypes.data, corners.ctypes.data, 0, 0)
+    score, r, filled = C.c_int(), SwResult(), C.c_uint32()
+    _check(lib().hclib_hip_sw_edges(s1, len(s1), s2, len(s2), tile_w, tile_h, C.byref(score), C.byref(r),
+                                    C.byref(e), C.byref(filled)), "hclib_hip_sw_edges")
+    m = filled.value
+    edges = {
+        "bottoms": bottoms if m & SW_EDGE_BOTTOMS else None,
+        # [nth][ntw][th] -> [ntw][nth*th]: tile column j's right column, top to bottom
+        "rights": (np.ascontiguousarray(rights.reshape(nth, ntw, tile_h).transpose(1, 0, 2))
+                   .reshape(ntw, nth * tile_h) if m & SW_EDGE_RIGHTS else None),
+        "corners": corners if m & SW_EDGE_CORNERS else None,
+        "path": SW_PATHS.get(e.path), "form": e.form,
+    }
+    return score.value, {k: getattr(r, k) for k, _ in SwResult._fields_}, edges
+
+
 class SwBand:
     """One rank's band of tile columns [j0, j1) of the SW tile grid
     (hclib_hip_sw_band_*, include/hclib_hip.h). rows() launches tile rows
@@ -544,6 +592,15 @@ class SwBand:
     def rows(self, i0: int, i1: int, left_in: int | None, right_out: int | None, stream: int):
         _check(lib().hclib_hip_sw_band_rows(self._h, i0, i1, left_in, right_out, stream),
                "hclib_hip_sw_band_rows")
+
+    def bottoms(self, stream: int):
+        """Before end(): synchronise and return the band's bottom rows, int32
+        [nth][(j1-j0)*tile_w] (H of matrix rows th, 2 th, ..., the band's columns)."""
+        import numpy as np
+
+        out = np.full((self.nth, (self.j1 - self.j0) * self.tile_w), -(1 << 30), dtype=np.int32)
+        _check(lib().hclib_hip_sw_band_bottoms(self._h, stream, out.ctypes.data), "hclib_hip_sw_band_bottoms")
+        return out
 
     def end(self, stream: int):
         """Synchronise, free; returns (bottom-right cell of the band, tiles run)."""

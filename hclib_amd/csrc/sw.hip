@@ -1818,8 +1818,36 @@ __global__ void k_sw_init(uint32_t *deps, uint32_t *ready, int ntw, int nth) {
 
 using namespace hx;
 
-extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw,
-                            int th, int *score, hclib_hip_sw_result_t *result) {
+// Tagged granules [n] from the device to plain H on the host (`h`, may be
+// null: only the last value of every `per_tile` run into `last`, may be null).
+// Row r of `rows` starts at dev + r * pitch granules and holds n / rows of
+// them; tile_of(k) names granule k's tile for the message. Every tag must be
+// set: an unwritten granule is an error, never a zero.
+template <class TileOf>
+static int sw_untag(const char *who, const char *what, const unsigned long long *dev, size_t n, size_t rows,
+                    size_t pitch, size_t per_tile, TileOf tile_of, int *h, int *last) {
+    std::vector<unsigned long long> g(n);
+    const size_t w = n / rows;
+    if (rows == 1) HX_HIP(hipMemcpy(g.data(), dev, n * 8, hipMemcpyDeviceToHost));
+    else HX_HIP(hipMemcpy2D(g.data(), w * 8, dev, pitch * 8, w * 8, rows, hipMemcpyDeviceToHost));
+    for (size_t k = 0; k < n; ++k) {
+        if ((g[k] >> 32) != 1ull) {
+            set_error("%s: %s granule of tile %zu, index %zu, was never put (tag %llu)", who, what, tile_of(k),
+                      k % per_tile, g[k] >> 32);
+            return HCLIB_HIP_EDEVICE;
+        }
+        if (h) h[k] = (int)(uint32_t)g[k];
+        if (last && k % per_tile == per_tile - 1) last[k / per_tile] = (int)(uint32_t)g[k];
+    }
+    return HCLIB_HIP_OK;
+}
+
+// hclib_hip_sw and hclib_hip_sw_edges: one body. `edges` null is
+// hclib_hip_sw as it always was; otherwise the tiles' outputs are copied to
+// the host after the run's synchronise and its checks.
+static int sw_run(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th, int *score,
+                  hclib_hip_sw_result_t *result, hclib_hip_sw_edges_t *edges, uint32_t *filled) {
+    if (filled) *filled = 0;
     if (!s1 || !s2 || !score || tw < 1 || th < 1 || tw > 16384) {
         set_error("hclib_hip_sw: invalid arguments (1 <= tw <= 16384, th >= 1)");
         return HCLIB_HIP_EINVAL;
@@ -1940,6 +1968,7 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
                             : (dag ? (const void *)k_sw_dag : (const void *)k_sw);
     if (lds > 64 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hclib_hip_dag_stats_t dst{};
+    int path = 0;  // HCLIB_HIP_SW_PATH_* (reported by hclib_hip_sw_edges)
     if (dag) {
         // the tile program's futures as a CSR over 3 promises per tile
         std::vector<uint32_t> off(nt + 1, 0), ids;
@@ -1954,6 +1983,7 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         // tile tasks on workgroups of th / 64 + 2 waves where the band
         // kernel applies (HCLIB_HIP_SW_DAG_WAVE=1: one wave per tile)
         const bool wg = band_shape && env_int("HCLIB_HIP_SW_DAG_WAVE", 0) == 0;
+        path = pk ? HCLIB_HIP_SW_PATH_DAG_PK : (wg ? HCLIB_HIP_SW_PATH_DAG_WG : HCLIB_HIP_SW_PATH_DAG_WAVE);
         hclib_hip_dag_launch_t L;
         HX_TRY(hclib_hip_dag_begin((uint32_t)nt, (uint32_t)(3 * nt), 0, nullptr, off.data(), ids.data(), nullptr,
                                    nullptr, pk ? env_int("HCLIB_HIP_SW_PK_WGS_PER_CU", 1)
@@ -1979,6 +2009,7 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         std::vector<uint8_t> sat(pk ? 3 * nt : 0);
         HX_TRY(hclib_hip_dag_end("hclib_hip_sw (dag)", nullptr, pk ? sat.data() : nullptr, &dst));
     } else {
+        path = band ? HCLIB_HIP_SW_PATH_BAND_ROWS : (rows ? HCLIB_HIP_SW_PATH_ROWS1 : HCLIB_HIP_SW_PATH_QUEUE);
         HX_HIP(hipEventRecord(m.ev0, m.stream));
         if (band) {
             const int k = sw_band_rows_per_wg(th, bh), nblk = ((int)nth + k - 1) / k;
@@ -2043,6 +2074,51 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         set_error("hclib_hip_sw: executed %llu of %zu tiles", st[0], nt);
         return HCLIB_HIP_EDEVICE;
     }
+    if (edges) {
+        // what each schedule leaves on the device (include/hclib_hip.h):
+        // granules (rows, packed) or the reference's plain arrays
+        const char *who = "hclib_hip_sw_edges";
+        const size_t per = (size_t)tw;
+        auto tile_tw = [per](size_t k) { return k / per; };
+        uint32_t have = 0;
+        edges->path = path;
+        edges->form = (band || path == HCLIB_HIP_SW_PATH_DAG_WG) ? form : 0;
+        if (rows || pk) {
+            // a band workgroup of several tile rows publishes only its last one
+            const bool all_rows = !(band && sw_band_rows_per_wg(th, bh) > 1);
+            int *cn = (rows && all_rows) ? edges->corners : nullptr;  // rows: the bottom row's last value
+            if (all_rows && (edges->bottoms || cn)) {
+                HX_TRY(sw_untag(who, "bottom-row", c.gbot, nt * per, 1, 0, per, tile_tw, edges->bottoms, cn));
+                if (edges->bottoms) have |= HCLIB_HIP_SW_EDGE_BOTTOMS;
+                if (cn) have |= HCLIB_HIP_SW_EDGE_CORNERS;
+            }
+            if (pk && edges->rights) {
+                const size_t ph = (size_t)th;
+                HX_TRY(sw_untag(who, "right-column", c.gright, nt * ph, 1, 0, ph,
+                                [ph](size_t k) { return k / ph; }, edges->rights, nullptr));
+                have |= HCLIB_HIP_SW_EDGE_RIGHTS;
+            }
+            if (pk && edges->corners) {
+                HX_TRY(sw_untag(who, "corner", c.gcorner, nt, 1, 0, 1, [](size_t k) { return k; }, edges->corners,
+                                nullptr));
+                have |= HCLIB_HIP_SW_EDGE_CORNERS;
+            }
+        } else {
+            if (edges->bottoms) {
+                HX_HIP(hipMemcpy(edges->bottoms, c.bottom, b_bot, hipMemcpyDeviceToHost));
+                have |= HCLIB_HIP_SW_EDGE_BOTTOMS;
+            }
+            if (edges->rights) {
+                HX_HIP(hipMemcpy(edges->rights, c.right, b_right, hipMemcpyDeviceToHost));
+                have |= HCLIB_HIP_SW_EDGE_RIGHTS;
+            }
+            if (edges->corners) {
+                HX_HIP(hipMemcpy(edges->corners, c.corner, b_c, hipMemcpyDeviceToHost));
+                have |= HCLIB_HIP_SW_EDGE_CORNERS;
+            }
+        }
+        if (filled) *filled = have;
+    }
     *score = corner;  // bottom_row[tw-1] of the last tile == its corner (:239)
     if (result) {
         result->tiles = st[0];
@@ -2053,6 +2129,23 @@ extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_
         result->release_us = st[0] ? (double)st[3] / st[0] / 2400.0 : 0.0;
     }
     return HCLIB_HIP_OK;
+}
+
+extern "C" int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw,
+                            int th, int *score, hclib_hip_sw_result_t *result) {
+    return sw_run(s1, n1, s2, n2, tw, th, score, result, nullptr, nullptr);
+}
+
+extern "C" int hclib_hip_sw_edges(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th,
+                                  int *score, hclib_hip_sw_result_t *result, hclib_hip_sw_edges_t *edges,
+                                  uint32_t *filled) {
+    if (!edges) {
+        set_error("hclib_hip_sw_edges: null edges (hclib_hip_sw runs without a read-back)");
+        return HCLIB_HIP_EINVAL;
+    }
+    edges->path = 0;
+    edges->form = 0;
+    return sw_run(s1, n1, s2, n2, tw, th, score, result, edges, filled);
 }
 
 // ------------------------------------------------- column-band sessions
@@ -2165,6 +2258,24 @@ extern "C" int hclib_hip_sw_band_rows(hclib_hip_sw_band_t *h, int i0, int i1, co
     else if (c.progressive) hipLaunchKernelGGL(k_sw_rows<true>, dim3(grid), dim3(64), h->lds, (hipStream_t)stream, c);
     else hipLaunchKernelGGL(k_sw_rows<false>, dim3(grid), dim3(64), h->lds, (hipStream_t)stream, c);
     return hip_check(hipGetLastError(), "k_sw_rows (band) launch");
+}
+
+extern "C" int hclib_hip_sw_band_bottoms(hclib_hip_sw_band_t *h, void *stream, int *out) {
+    if (!h || !out) {
+        set_error("hclib_hip_sw_band_bottoms: null %s", h ? "output" : "band");
+        return HCLIB_HIP_EINVAL;
+    }
+    HX_TRY(hip_check(hipStreamSynchronize((hipStream_t)stream), "k_sw_rows (band)"));
+    const SwCtx &c = h->c;
+    uint32_t herr = 0;
+    HX_HIP(hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost));
+    if (herr) {
+        set_error("hclib_hip_sw_band_bottoms: device error %u", herr);
+        return HCLIB_HIP_EDEVICE;
+    }
+    const size_t per = (size_t)c.tw, w = (size_t)(c.j1 - c.j0) * per, ntw = (size_t)c.ntw, j0 = (size_t)c.j0;
+    return sw_untag("hclib_hip_sw_band_bottoms", "bottom-row", c.gbot + j0 * per, (size_t)c.nth * w, (size_t)c.nth,
+                    ntw * per, per, [=](size_t k) { return (k / w) * ntw + j0 + (k % w) / per; }, out, nullptr);
 }
 
 extern "C" int hclib_hip_sw_band_end(hclib_hip_sw_band_t *h, void *stream, int *corner, uint64_t *tiles) {

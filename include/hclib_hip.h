@@ -546,6 +546,47 @@ typedef struct {
 int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th,
                  int *score, hclib_hip_sw_result_t *result);
 
+/* The same run, plus a read-back of what every tile put (the reference's
+ * three promises per tile, smith_waterman.cpp:212-226), for tests: H values,
+ * copied from the device after the run's own synchronise; no kernel differs.
+ * The pointers are optional host arrays; `*filled` (may be NULL) receives the
+ * HCLIB_HIP_SW_EDGE_* bits of the arrays that were given AND that the
+ * schedule that ran keeps on the device:
+ *   bottoms [nth][ntw*tw]  H(matrix row (i+1)*th, columns 1..ntw*tw): every
+ *                          schedule, except the multi-wave row kernel with
+ *                          HCLIB_HIP_SW_ROWS_PER_WG > 1 (a workgroup then
+ *                          publishes only its last tile row; bit clear);
+ *   rights  [tiles][th]    tile t = i*ntw + j: H(rows i*th+1 .. (i+1)*th,
+ *                          column (j+1)*tw): the queue and every promise-DAG
+ *                          body. The row schedules keep right columns in LDS
+ *                          only: bit clear, array untouched;
+ *   corners [tiles]        H((i+1)*th, (j+1)*tw): the tile's own corner word
+ *                          (queue, DAG bodies), or the last value of its
+ *                          bottom row where the schedule keeps no corner word
+ *                          (row schedules; clear when bottoms is).
+ * Where the device holds tagged granules, every tag must be set: a granule
+ * without its tag is HCLIB_HIP_EDEVICE, the message naming tile and index.
+ * `path` / `form` report what ran: HCLIB_HIP_SW_PATH_*, and the multi-wave
+ * band form (100 R + 10 S + K / 16, after the fallback for th) or 0. */
+#define HCLIB_HIP_SW_EDGE_BOTTOMS 1u
+#define HCLIB_HIP_SW_EDGE_RIGHTS 2u
+#define HCLIB_HIP_SW_EDGE_CORNERS 4u
+#define HCLIB_HIP_SW_PATH_QUEUE 1     /* one wave per tile, dependency counters */
+#define HCLIB_HIP_SW_PATH_ROWS1 2     /* row schedule, one wave per tile row */
+#define HCLIB_HIP_SW_PATH_BAND_ROWS 3 /* row schedule, multi-wave band rows */
+#define HCLIB_HIP_SW_PATH_DAG_WAVE 4  /* promise DAG, one wave per tile */
+#define HCLIB_HIP_SW_PATH_DAG_WG 5    /* promise DAG, band workgroup per tile */
+#define HCLIB_HIP_SW_PATH_DAG_PK 6    /* promise DAG, packed-half body */
+typedef struct {
+    int *bottoms;
+    int *rights;
+    int *corners;
+    int path; /* out */
+    int form; /* out */
+} hclib_hip_sw_edges_t;
+int hclib_hip_sw_edges(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th, int *score,
+                       hclib_hip_sw_result_t *result, hclib_hip_sw_edges_t *edges, uint32_t *filled);
+
 /* Column-band session (multi-GPU SW, one band of tile columns per rank).
  * The reference runs the whole tile DAG in one address space
  * (smith_waterman.cpp:168-235); sharded, rank r owns tile columns [j0, j1)
@@ -560,12 +601,19 @@ int hclib_hip_sw(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int t
  *           ints, or NULL) receives H of column j1*tw for the same rows;
  *   end     synchronises the stream, checks the device error word, writes
  *           the band's bottom-right cell (the score for the last band) and
- *           the tiles executed, and frees the band. */
+ *           the tiles executed, and frees the band;
+ *   bottoms (for tests, before end) synchronises the stream and copies the
+ *           band's bottom rows to the host array out[nth][(j1-j0)*tw]: H of
+ *           matrix rows (i+1)*th, columns j0*tw+1 .. j1*tw. Every tile row
+ *           must have been launched, one tile row per workgroup
+ *           (HCLIB_HIP_SW_ROWS_PER_WG unset or 1): a granule without its tag
+ *           is HCLIB_HIP_EDEVICE, the message naming tile and index. */
 typedef struct hclib_hip_sw_band hclib_hip_sw_band_t;
 int hclib_hip_sw_band_begin(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th,
                             int j0, int j1, hclib_hip_sw_band_t **band);
 int hclib_hip_sw_band_rows(hclib_hip_sw_band_t *band, int i0, int i1, const int *left_in, int *right_out,
                            void *stream);
+int hclib_hip_sw_band_bottoms(hclib_hip_sw_band_t *band, void *stream, int *out);
 int hclib_hip_sw_band_end(hclib_hip_sw_band_t *band, void *stream, int *corner, uint64_t *tiles);
 
 /* ----------------------------------------------------------- Cholesky */

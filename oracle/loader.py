@@ -79,7 +79,7 @@ _libs: dict = {}
 # the newest entry point each library must export: a library built from an
 # older source (a kept _build/ directory) is rebuilt instead of failing at the
 # first call of a symbol it lacks
-_NEWEST_SYMBOL = {"liboracle.so": b"ora_uts_serial_shard", "libhclib_cpu.so": b"ora_uts_serial_shard"}
+_NEWEST_SYMBOL = {"liboracle.so": b"ora_sw_edges","libhclib_cpu.so": b"ora_uts_serial_shard"}
 _checked = False
 
 
@@ -194,6 +194,26 @@ def sw_score(s1: bytes, s2: bytes, tw: int, th: int, want_edges: bool = False):
     if want_edges:
         return score, list(lr), list(lc)
     return score
+
+
+def sw_edges(s1: bytes, s2: bytes, tw: int, th: int):
+    """ora_sw_edges: (score, rows [nth][W], cols [ntw][R], corners [nth][ntw])
+    as int32 arrays — every th-th matrix row, every tw-th matrix column and
+    their crossings, from the plain recurrence."""
+    import numpy as np
+
+    lib = oracle()
+    ntw, nth = len(s1) // tw, len(s2) // th
+    W, R = ntw * tw, nth * th
+    rows = np.zeros((nth, W), dtype=np.int32)
+    cols = np.zeros((ntw, R), dtype=np.int32)
+    corners = np.zeros((nth, ntw), dtype=np.int32)
+    ip = C.POINTER(C.c_int)
+    lib.ora_sw_edges.restype = C.c_int
+    lib.ora_sw_edges.argtypes = [C.c_char_p, C.c_size_t, C.c_char_p, C.c_size_t, C.c_int, C.c_int, ip, ip, ip]
+    score = lib.ora_sw_edges(s1, len(s1), s2, len(s2), tw, th, rows.ctypes.data_as(ip),
+                             cols.ctypes.data_as(ip), corners.ctypes.data_as(ip))
+    return score, rows, cols, corners
 
 
 def fib_iter(n: int) -> int:

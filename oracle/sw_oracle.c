@@ -76,6 +76,51 @@ int ora_sw_score(const signed char *s1, size_t n1, const signed char *s2, size_t
     return score;
 }
 
+/* What every tile of that DAG puts (smith_waterman.cpp:212-226), from the
+ * same plain recurrence over the whole matrix (no transformed values, no
+ * tiling): rows [nth][W] = H[(i+1)*th][1..W] (the tiles' bottom rows),
+ * cols [ntw][R] = H[1..R][(j+1)*tw] (their right columns) and
+ * corners [nth][ntw] = H[(i+1)*th][(j+1)*tw]; each optional. Returns the
+ * score H[R][W]. */
+int ora_sw_edges(const signed char *s1, size_t n1, const signed char *s2, size_t n2, int tw, int th,
+                 int *rows, int *cols, int *corners) {
+    size_t ntw = n1 / (size_t)tw, nth = n2 / (size_t)th;
+    size_t W = ntw * (size_t)tw, R = nth * (size_t)th;
+    int *prev = (int *)malloc((W + 1) * sizeof(int));
+    int *cur = (int *)malloc((W + 1) * sizeof(int));
+    if (!prev || !cur) {
+        free(prev);
+        free(cur);
+        return 0;
+    }
+    for (size_t c = 0; c <= W; c++) prev[c] = -(int)c;
+    for (size_t r = 1; r <= R; r++) {
+        const signed char *m = ora_sw_matrix[s2[r - 1]];
+        cur[0] = -(int)r;
+        for (size_t c = 1; c <= W; c++) {
+            int v = prev[c - 1] + m[s1[c - 1]];
+            if (cur[c - 1] - 1 > v) v = cur[c - 1] - 1;
+            if (prev[c] - 1 > v) v = prev[c] - 1;
+            cur[c] = v;
+        }
+        if (cols)
+            for (size_t j = 0; j < ntw; j++) cols[j * R + (r - 1)] = cur[(j + 1) * (size_t)tw];
+        if (r % (size_t)th == 0) {
+            size_t i = r / (size_t)th - 1;
+            if (rows) memcpy(rows + i * W, cur + 1, W * sizeof(int));
+            if (corners)
+                for (size_t j = 0; j < ntw; j++) corners[i * ntw + j] = cur[(j + 1) * (size_t)tw];
+        }
+        int *t = prev;
+        prev = cur;
+        cur = t;
+    }
+    int score = prev[W];
+    free(prev);
+    free(cur);
+    return score;
+}
+
 /* fib_iter, test/fib/fib.c:38-46 */
 long ora_fib_iter(int n) {
     int i, x, y;

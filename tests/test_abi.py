@@ -175,6 +175,40 @@ def test_sw_band_checks_arguments_then_needs_a_gpu():
             H.SwBand(s, s, 64, 64, 1, 3)
 
 
+def test_sw_edges_check_arguments_then_need_a_gpu():
+    """hclib_hip_sw_edges / hclib_hip_sw_band_bottoms: a null edges struct, a
+    null score, a null band and a null output are rejected on the host, and
+    hclib_hip_sw_edges checks its sequences as hclib_hip_sw does; without a
+    gfx950 device a valid call fails with ENODEV — no CPU fallback."""
+    import torch
+
+    lib = H.lib()
+    s = bytes([1, 2, 3, 4] * 64)
+    score, filled, e = C.c_int(), C.c_uint32(7), H.SwEdges()
+    with pytest.raises(H.HclibError, match="null edges"):
+        H._check(lib.hclib_hip_sw_edges(s, len(s), s, len(s), 64, 64, C.byref(score), None, None,
+                                        C.byref(filled)), "edges")
+    with pytest.raises(H.HclibError, match="invalid"):
+        H._check(lib.hclib_hip_sw_edges(s, len(s), s, len(s), 64, 64, None, None, C.byref(e),
+                                        C.byref(filled)), "edges")
+    assert filled.value == 0  # nothing filled on a refused call
+    with pytest.raises(H.HclibError, match="invalid"):
+        H._check(lib.hclib_hip_sw_edges(None, len(s), s, len(s), 64, 64, C.byref(score), None, C.byref(e),
+                                        None), "edges")
+    with pytest.raises(H.HclibError, match="coded"):
+        H.sw_edges(bytes(256), s, 64, 64)
+    with pytest.raises(H.HclibError, match="empty"):
+        H.sw_edges(s, s, 512, 64)
+    with pytest.raises(H.HclibError, match="null band"):
+        H._check(lib.hclib_hip_sw_band_bottoms(None, None, None), "bottoms")
+    out = (C.c_int * 4)()
+    with pytest.raises(H.HclibError, match="null band"):
+        H._check(lib.hclib_hip_sw_band_bottoms(None, None, out), "bottoms")
+    if not torch.cuda.is_available():
+        with pytest.raises(H.HclibError):
+            H.sw_edges(s, s, 64, 64)
+
+
 def test_global_region_layout_and_no_gpu_failures():
     """Cross-GPU sharing region (hclib_hip_global_*): its size is a host-side
     function of the slot count (header + {seq, cnt} pairs + 2-KiB chunk

@@ -512,10 +512,12 @@ def test_sw_multiwave_tile_rows(n1, n2, tw, th, monkeypatch):
     assert H.sw(s1, s2, tw, th)[0] == want
 
 
-def _sw_bands_in_order(s1, s2, tw, th, nbands, block_rows):
+def _sw_bands_in_order(s1, s2, tw, th, nbands, block_rows, before_end=None):
     """Every band of an nbands-way column split, run one after the other on
     cuda:0 through hclib_hip_sw_band_* in blocks of tile rows; band r's left
-    column is band r-1's right column (what ShardedSw moves between ranks)."""
+    column is band r-1's right column (what ShardedSw moves between ranks).
+    before_end(band, stream), if given, sees each band once all its rows are
+    launched (tests/test_sw_edges_gpu.py reads its bottom rows there)."""
     import torch
 
     from hclib_amd import dist
@@ -531,6 +533,8 @@ def _sw_bands_in_order(s1, s2, tw, th, nbands, block_rows):
         for i0, i1 in dist.sw_blocks(nth, block_rows):
             band.rows(i0, i1, None if left is None else left.data_ptr(),
                       None if right is None else right.data_ptr(), stream)
+        if before_end is not None:
+            before_end(band, stream)
         score, t = band.end(stream)
         tiles += t
         rights.append((j1, None if right is None else right.cpu().tolist()))
