@@ -160,6 +160,33 @@ class HealthState(C.Structure):
     _fields_ = [(k, C.c_void_p) for k in ("seed", "time", "time_left", "hosps_visited", "village", "lists")]
 
 
+FLOORPLAN_MAX_CELLS, FLOORPLAN_MAX_SHAPES = 20, 8  # include/hclib_hip.h
+
+
+class FloorplanInput(C.Structure):
+    """hclib_hip_floorplan_input_t: arrays by cell id 1..n (entry 0 unused)."""
+
+    _fields_ = [("n", C.c_int32), ("solution", C.c_int32), ("shapes", C.c_int32 * (FLOORPLAN_MAX_CELLS + 1)),
+                ("shape", C.c_int32 * 2 * FLOORPLAN_MAX_SHAPES * (FLOORPLAN_MAX_CELLS + 1)),
+                ("left", C.c_int32 * (FLOORPLAN_MAX_CELLS + 1)), ("above", C.c_int32 * (FLOORPLAN_MAX_CELLS + 1)),
+                ("next", C.c_int32 * (FLOORPLAN_MAX_CELLS + 1))]
+
+
+class FloorplanPlacement(C.Structure):
+    """hclib_hip_floorplan_placement_t."""
+
+    _fields_ = [("shape", C.c_int32), ("top", C.c_int32), ("lhs", C.c_int32)]
+
+
+class FloorplanResult(C.Structure):
+    """hclib_hip_floorplan_result_t."""
+
+    _fields_ = [("min_area", C.c_int32), ("footprint", C.c_int32 * 2),
+                ("placements", FloorplanPlacement * FLOORPLAN_MAX_CELLS)] + \
+               [(k, C.c_uint64) for k in ("tasks", "items", "laid", "complete", "improvements", "chunks_pushed",
+                                          "chunks_stolen")] + [("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -185,6 +212,7 @@ EXPORTS_HIP = [
     "hclib_hip_nqueens", "hclib_hip_nqueens_bounds",
     "hclib_hip_strassen", "hclib_hip_strassen_bounds", "hclib_hip_strassen_last_ticks",
     "hclib_hip_health", "hclib_hip_health_bounds", "hclib_hip_health_last_ticks",
+    "hclib_hip_floorplan", "hclib_hip_floorplan_read_input",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -269,6 +297,9 @@ def lib():
                                                    C.POINTER(C.c_double)]
         L.hclib_hip_nqueens.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(NQueensResult), C.POINTER(C.c_uint64)]
         L.hclib_hip_nqueens_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_floorplan.argtypes = [C.POINTER(FloorplanInput), C.c_int, C.POINTER(FloorplanResult), C.c_void_p,
+                                          C.POINTER(C.c_uint64)]
+        L.hclib_hip_floorplan_read_input.argtypes = [C.c_char_p, C.POINTER(FloorplanInput)]
         L.hclib_hip_strassen.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                          C.POINTER(StrassenResult)]
         L.hclib_hip_strassen_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
@@ -990,6 +1021,66 @@ def health_last_ticks() -> dict:
     out = (C.c_uint64 * 3)()
     lib().hclib_hip_health_last_ticks(out)
     return dict(zip(("leaf_call", "inner_call", "post"), out))
+
+
+# ------------------------------------------------------------ BOTS floorplan
+FLOORPLAN_NOPRUNE = 1  # HCLIB_HIP_FLOORPLAN_NOPRUNE
+
+
+def _floorplan_input(cells) -> FloorplanInput:
+    """cells: one (shapes, left, above, next) per cell 1..n, shapes a list of
+    (rows, cols). What does not fit the struct is left for the library to
+    refuse (a count it can see is kept, the surplus is dropped)."""
+    if isinstance(cells, FloorplanInput):
+        return cells
+    inp = FloorplanInput()
+    inp.n, inp.solution = len(cells), -1
+    for c, (shapes, left, above, nxt) in enumerate(cells[:FLOORPLAN_MAX_CELLS], 1):
+        inp.shapes[c] = len(shapes)
+        for i, (rows, cols) in enumerate(shapes[:FLOORPLAN_MAX_SHAPES]):
+            inp.shape[c][i][0], inp.shape[c][i][1] = rows, cols
+        inp.left[c], inp.above[c], inp.next[c] = left, above, nxt
+    return inp
+
+
+def floorplan_read_input(path):
+    """A BOTS floorplan input file (read_inputs, floorplan.c:159-195) through
+    hclib_hip_floorplan_read_input, on the host alone. Returns (cells,
+    solution): cells as floorplan() takes them, solution the file's trailing
+    expected minimum area or -1."""
+    inp = FloorplanInput()
+    _check(lib().hclib_hip_floorplan_read_input(os.fsencode(path), C.byref(inp)), "hclib_hip_floorplan_read_input")
+    cells = [([(inp.shape[c][i][0], inp.shape[c][i][1]) for i in range(inp.shapes[c])], inp.left[c], inp.above[c],
+              inp.next[c]) for c in range(1, inp.n + 1)]
+    return cells, inp.solution
+
+
+def floorplan(cells_or_path, prune: bool = True, hist: bool = False) -> dict:
+    """BOTS floorplan on the work-stealing scheduler (hclib_hip_floorplan): the
+    branch-and-bound search for the smallest bounding box of the cells, one
+    task per (shape, corner) candidate, pruned against a bound the tasks lower
+    while they run. cells_or_path: a cell table (see floorplan_read_input) or
+    an input file. prune=False compares against the constant 4096: exhaustive,
+    every count deterministic. Returns the fields of
+    hclib_hip_floorplan_result_t with "footprint" a list, "placements" one
+    [shape, top, lhs] per cell (None without a complete placement), "board"
+    the 4096 bytes of the best board and, with hist, "hist": the candidates
+    laid down per depth 0..n."""
+    cells = floorplan_read_input(cells_or_path)[0] if isinstance(cells_or_path, (str, bytes, os.PathLike)) \
+        else cells_or_path
+    inp = _floorplan_input(cells)
+    r = FloorplanResult()
+    board = (C.c_uint8 * 4096)()
+    h = (C.c_uint64 * (FLOORPLAN_MAX_CELLS + 1))() if hist else None
+    _check(lib().hclib_hip_floorplan(C.byref(inp), 0 if prune else FLOORPLAN_NOPRUNE, C.byref(r), board, h),
+           "hclib_hip_floorplan")
+    out = {k: getattr(r, k) for k, _ in FloorplanResult._fields_ if k not in ("footprint", "placements")}
+    out["footprint"] = list(r.footprint)
+    out["placements"] = [[p.shape, p.top, p.lhs] for p in r.placements[:inp.n]] if r.min_area < 4096 else None
+    out["board"] = bytes(board)
+    if hist:
+        out["hist"] = list(h)[:inp.n + 1]
+    return out
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

@@ -58,6 +58,12 @@
  *                                    with its five list walks as wave-wide
  *                                    partitions, every round of the same fork-join
  *                                    tree in one launch of dynamic device dataflow
+ *   hclib_hip_floorplan              the async per (shape, corner) candidate, the
+ *                                    pruning against MIN_AREA and the critical
+ *                                    section of BOTS floorplan (bots/floorplan/
+ *                                    floorplan.c:230-328), as a task kind of the
+ *                                    work-stealing megakernel with the bound as one
+ *                                    word every XCD reads and lowers
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -896,6 +902,69 @@ int hclib_hip_health(const hclib_hip_health_params_t *params, hclib_hip_health_r
                      hclib_hip_health_state_t *state /* may be NULL */);
 int hclib_hip_health_bounds(const hclib_hip_health_params_t *params, uint64_t out[6]);
 void hclib_hip_health_last_ticks(uint64_t out[3]);
+
+/* ------------------------------------------------------------ Floorplan */
+/* BOTS floorplan (test/performance-regression/full-apps/bots/floorplan:
+ * floorplan.c:230-328, the algorithm in floorplan.ref.c) on the persistent
+ * work-stealing scheduler: a branch-and-bound search for the smallest bounding
+ * box of n cells on a 64 x 64 board. Each cell has up to 8 shapes and is placed
+ * against its `left` and / or `above` cell (0: the dummy cell, which puts cell
+ * 1 in column 0; -1: none), in the order 1, next[1], ... One task per (shape,
+ * north-west corner) candidate, in the reference's order; a candidate that is
+ * not the last cell spawns the next cell's candidates iff its area is below
+ * the bound, one word that complete placements lower while the search runs.
+ * The input's arrays are indexed by cell id 1..n (entry 0 is ignored).
+ * flags: HCLIB_HIP_FLOORPLAN_NOPRUNE compares against the constant 4096
+ * instead (the bound is still tracked): the search is exhaustive and every
+ * count is the same on every run. Pruned, min_area and its footprint are
+ * deterministic; the counts and, among placements of equal area, the one
+ * returned depend on the schedule, as in the reference.
+ * result: min_area (4096 and a 0 x 0 footprint when no complete placement
+ * exists, as the reference prints), footprint = {rows, columns}, placements
+ * [id - 1] = the shape index and north-west corner of cell id (-1s without a
+ * placement). tasks = the candidates spawned (bots_number_of_tasks), items =
+ * what the device ran (every candidate is one item: items == tasks), laid =
+ * candidates that were laid down, complete = complete placements reached,
+ * improvements = successful lowerings of the bound.
+ * board (4096 bytes, or NULL): the best board, row-major, cell ids, 0 empty.
+ * hist (n + 1 entries, or NULL): hist[d] = candidates of the d-th cell of the
+ * chain that were laid down (hist[0] = 0); a separate kernel instantiation.
+ * A rectangle that leaves the board does not fit (the reference indexes past
+ * its board there).
+ * HCLIB_HIP_EINVAL before the device is touched: n < 1 or n > 20; a cell with
+ * fewer than 1 or more than 8 shapes; a shape dimension outside 1..64; left,
+ * above or next outside the table; a cell with neither left nor above, or one
+ * that depends on a cell the chain places later (the reference reads
+ * rectangles that do not exist); a next chain from cell 1 that does not visit
+ * every cell exactly once before 0; result NULL; an unknown flag.
+ * hclib_hip_floorplan_read_input: host only, no GPU: the reference's file
+ * format (read_inputs, floorplan.c:159-195) with the optional trailing
+ * expected minimum area (solution, -1 without one), checked as above. */
+#define HCLIB_HIP_FLOORPLAN_MAX_CELLS 20
+#define HCLIB_HIP_FLOORPLAN_MAX_SHAPES 8
+#define HCLIB_HIP_FLOORPLAN_NOPRUNE 1
+typedef struct {
+    int32_t n;
+    int32_t solution; /* the file's expected minimum area, or -1 */
+    int32_t shapes[HCLIB_HIP_FLOORPLAN_MAX_CELLS + 1];
+    int32_t shape[HCLIB_HIP_FLOORPLAN_MAX_CELLS + 1][HCLIB_HIP_FLOORPLAN_MAX_SHAPES][2]; /* rows, columns */
+    int32_t left[HCLIB_HIP_FLOORPLAN_MAX_CELLS + 1];
+    int32_t above[HCLIB_HIP_FLOORPLAN_MAX_CELLS + 1];
+    int32_t next[HCLIB_HIP_FLOORPLAN_MAX_CELLS + 1];
+} hclib_hip_floorplan_input_t;
+typedef struct {
+    int32_t shape, top, lhs;
+} hclib_hip_floorplan_placement_t;
+typedef struct {
+    int32_t min_area;
+    int32_t footprint[2];
+    hclib_hip_floorplan_placement_t placements[HCLIB_HIP_FLOORPLAN_MAX_CELLS];
+    uint64_t tasks, items, laid, complete, improvements, chunks_pushed, chunks_stolen;
+    double kernel_ms, busy_frac;
+} hclib_hip_floorplan_result_t;
+int hclib_hip_floorplan(const hclib_hip_floorplan_input_t *in, int flags, hclib_hip_floorplan_result_t *result,
+                        uint8_t *board /* 4096, may be NULL */, uint64_t *hist /* n + 1, may be NULL */);
+int hclib_hip_floorplan_read_input(const char *path, hclib_hip_floorplan_input_t *out);
 
 #ifdef __cplusplus
 }
