@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "hx_module.h"
+#include "hx_sw_plan.h"
 #include "../../include/hclib_hip/hx_dag.h"
 
 namespace hx {
@@ -426,6 +427,7 @@ __device__ bool sw_tile(const SwCtx &c, uint32_t t, int *lds_top, int *lds_bot, 
 }
 
 __global__ __launch_bounds__(64) void k_sw(SwCtx c) {
+    // the host sizes this layout with sw_tile_lds_bytes(tw, th, false) (hx_sw_plan.h)
     extern __shared__ __attribute__((aligned(16))) int sw_lds[];
     int *lds_top = sw_lds;
     int *lds_bot = sw_lds + ((c.tw + 1 + 3) & ~3);
@@ -503,6 +505,7 @@ __global__ __launch_bounds__(64) void k_sw(SwCtx c) {
 // order, so each wait ends.
 template <bool PROG>
 __global__ __launch_bounds__(64) void k_sw_rows(SwCtx c) {
+    // the host sizes this layout with sw_tile_lds_bytes(tw, th, true) (hx_sw_plan.h)
     extern __shared__ __attribute__((aligned(16))) int sw_lds[];
     int *lds_top = sw_lds;
     int *lds_bot = sw_lds + ((c.tw + 1 + 3) & ~3);
@@ -560,44 +563,9 @@ __global__ __launch_bounds__(64) void k_sw_rows(SwCtx c) {
 // written, cons[w] = columns of ring w read, so wave w + 1 runs 64 + kSwSub
 // steps behind wave w. NW waves run on the CU's 4 SIMDs at once instead of
 // one wave per tile row.
-constexpr int kSwRing = 512;  // columns per inter-wave ring (+1 wrap slot)
-constexpr int kSwRingStride = kSwRing + 4;
+// (kSwRing columns per inter-wave ring, kSwDummy dummy slots per compute wave,
+// the LDS bytes and the form rules: hx_sw_plan.h)
 constexpr int kSwSub = 16;    // steps per hand-off
-// dummy ring slots per compute wave (its lanes 0..62 write there every step
-// while lane 63 writes the out ring; lane stride 1: neighbours' two-dword
-// writes overlap, which measured no slower than stride 2)
-constexpr int kSwDummy = 128;
-
-__host__ __device__ inline size_t sw_band_lds_bytes(int nw) {
-    return (size_t)(nw + 1) * kSwRingStride * 4  // rings
-           + (size_t)nw * kSwDummy * 4            // per-wave dummy slots (lanes 0..62's ring writes)
-           + (size_t)nw * 2048                    // per-wave code rings: 4 byte-shifted copies, double-mapped
-           + 2 * 64 * 4;                          // prod / cons words
-}
-
-// the multi-wave kernel's shape: bands of bh = 64 or 128 rows, 1..14 compute
-// waves per tile row (+ the ingress and egress waves)
-inline bool sw_band_ok(int th, int bh) { return th % bh == 0 && th / bh >= 1 && th / bh <= 14; }
-// HCLIB_HIP_SW_FORM (default `def`), kept to a valid form for th: two rows
-// per lane need th % 128 == 0, else one row per lane with the same hand-off
-inline int sw_pick_form(int th, int def) {
-    int form = env_int("HCLIB_HIP_SW_FORM", def);
-    if (form != 11 && form != 12 && form != 14 && form != 21 && form != 22 && form != 211 && form != 212 &&
-        form != 214 && form != 411 && form != 412 && form != 414)
-        form = def;
-    if (form > 400 && th % 256 != 0) form -= 200;
-    if (form > 200 && th % 128 != 0) form -= 200;
-    return form;
-}
-inline int sw_form_bh(int form) { return 64 * (form > 100 ? form / 100 : 1); }
-// tile rows per workgroup (HCLIB_HIP_SW_ROWS_PER_WG, default 1): more share
-// the CU's SIMDs between more waves and measured slower (scripts/probe_sw.py)
-inline int sw_band_rows_per_wg(int th, int bh) {
-    const int bpt = th / bh, most = 14 / bpt;
-    int k = env_int("HCLIB_HIP_SW_ROWS_PER_WG", 1);
-    return k < 1 ? 1 : (k > most ? most : k);
-}
-
 // Flags between the waves of a workgroup. The LDS performs one wave's DS
 // operations in issue order, so a flag stored after the ring data is seen
 // after that data by any wave that reads the flag first and the data next;
@@ -1118,6 +1086,7 @@ __global__ __launch_bounds__(1024) void k_sw_band_rows(SwCtx c) {
 struct SwDagKind {
     using Ctx = SwCtx;
     __device__ static void run(const SwCtx &c, DagWave &w, uint32_t t, const uint32_t *) {
+        // k_sw's layout: sw_tile_lds_bytes(tw, th, false) (hx_sw_plan.h)
         extern __shared__ __attribute__((aligned(16))) int sw_lds[];
         int *lds_top = sw_lds;
         int *lds_bot = sw_lds + ((c.tw + 1 + 3) & ~3);
@@ -1283,14 +1252,8 @@ __device__ __forceinline__ uint32_t sw_pk_row(int a) {
     return a == 1 ? 0xC000C044u : a == 2 ? 0x00C044C0u : a == 3 ? 0xC044C000u : 0x44C000C0u;
 }
 constexpr uint32_t kSwPkNull = 0x0Cu;  // v_perm selector byte of a constant 0x00
-constexpr int kSwPkTh = 256;            // tile rows the packed body covers
-constexpr int kSwPkMaxTw = 512;         // f16 exactness bound (see above)
-// LDS words of the packed body's arrays for tiles ncols wide: the top row
-// (x < ncols + 196, zeros past the tile) and four copies of the per-column
-// permute selectors (x in [-64, ncols + 200)), copy o at word x + 64 + o
-__host__ __device__ constexpr int sw_pk_topw(int ncols) { return (ncols + 196 + 3) & ~3; }
-__host__ __device__ constexpr int sw_pk_selw(int ncols) { return (ncols + 268 + 3) & ~3; }
-
+// (kSwPkTh = 256 tile rows, kSwPkMaxTw = 512, the f16 exactness bound above,
+// and the LDS words of the arrays below: hx_sw_plan.h)
 // Inputs and outputs in global memory are tagged granules {1 << 32 | H}:
 // a reader polls the tags, so the producing tile's put need not wait for its
 // stores to drain (SwDagPkKind::kTagged).
@@ -1323,20 +1286,10 @@ struct SwPkTile {
 // instruction count: moving the two lookups (v_perm) and the selector loads
 // to a second wave leaves the sweep rot + up + 2 adds + 2 max3 + half a
 // gather and half a ring load per step.
-// Ring: kSwPkSlots chunks of 64 steps; a chunk is 32 step pairs x 64 lanes of
-// uint4 {sc0(2p), sc1(2p), sc0(2p+1), sc1(2p+1)}. misc[5] = chunks written,
-// misc[6] = chunks read (both reset between tiles).
-constexpr int kSwPkSlots = 2;
+// Ring: kSwPkSlots chunks of 64 steps (hx_sw_plan.h).
 // the sweep's operand prefetch distance (groups of 4 steps; 1-3 measured
 // flat, profiles/r03/sw_pk_prefetch_ab.log)
 constexpr int kSwPkPf = 3;
-constexpr int kSwPkRingU4 = kSwPkSlots * 32 * 64;  // uint4 entries
-// LDS: ring | top | sel x 4 | right columns [2][256] | misc[16] | score rows [4][64] | next top row [512]
-constexpr int kSwPkMisc = 16;
-__host__ __device__ constexpr int sw_pk_lds_words(int tw) {
-    return kSwPkRingU4 * 4 + sw_pk_topw(tw) + 4 * sw_pk_selw(tw) + 2 * kSwPkTh + kSwPkMisc + 256 + kSwPkMaxTw;
-}
-inline size_t sw_pk_lds_bytes(int tw) { return (size_t)sw_pk_lds_words(tw) * 4; }
 
 // wait until an LDS counter reaches `want` (bounded; device error on timeout)
 // EQ: wait for the flag to equal `want` (a per-tile flag whose tiles are not
@@ -1842,77 +1795,73 @@ static int sw_untag(const char *who, const char *what, const unsigned long long 
     return HCLIB_HIP_OK;
 }
 
-// hclib_hip_sw and hclib_hip_sw_edges: one body. `edges` null is
-// hclib_hip_sw as it always was; otherwise the tiles' outputs are copied to
-// the host after the run's synchronise and its checks.
-static int sw_run(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th, int *score,
-                  hclib_hip_sw_result_t *result, hclib_hip_sw_edges_t *edges, uint32_t *filled) {
-    if (filled) *filled = 0;
-    if (!s1 || !s2 || !score || tw < 1 || th < 1 || tw > 16384) {
-        set_error("hclib_hip_sw: invalid arguments (1 <= tw <= 16384, th >= 1)");
+// the kernels' error word, as `who`'s error
+static int sw_device_error(const char *who, const SwCtx &c) {
+    uint32_t herr = 0;
+    HX_HIP(hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost));
+    if (herr) set_error("%s: device error %u", who, herr);
+    return herr ? HCLIB_HIP_EDEVICE : HCLIB_HIP_OK;
+}
+
+// ------------------------------------------------------- the run's steps
+// hx_sw_plan.h decides what a run launches; the steps below carry a plan out
+// and never ask again which path it is beyond the plan's own fields.
+
+// the HCLIB_HIP_SW_* knobs, as the environment has them now
+static SwKnobs sw_knobs() {
+    SwKnobs k;
+    const char *s = getenv("HCLIB_HIP_SW_SCHED");
+    static const char *const kSched[] = {"rows", "rows1", "queue", "dag"};  // SwSched's order; any other word: rows
+    for (int i = 1; s && i < 4; ++i) if (!strcmp(s, kSched[i])) k.sched = (SwSched)i;
+    static const struct { const char *name; int SwKnobs::*field; } kEnv[] = {
+        {"HCLIB_HIP_SW_FORM", &SwKnobs::form}, {"HCLIB_HIP_SW_PK", &SwKnobs::pk},
+        {"HCLIB_HIP_SW_DAG_WAVE", &SwKnobs::dag_wave}, {"HCLIB_HIP_SW_PROGRESSIVE", &SwKnobs::progressive},
+        {"HCLIB_HIP_SW_ROWS_PER_WG", &SwKnobs::rows_per_wg}, {"HCLIB_HIP_SW_WAVES_PER_CU", &SwKnobs::waves_per_cu},
+        {"HCLIB_HIP_SW_PK_WGS_PER_CU", &SwKnobs::pk_wgs_per_cu}, {"HCLIB_HIP_SW_DAG_WGS_PER_CU", &SwKnobs::dag_wgs_per_cu}};
+    for (const auto &e : kEnv) k.*e.field = env_int(e.name, k.*e.field);
+    return k;
+}
+
+// Arguments, tile grid and sequence coding, for `who`'s messages. `ptrs`: the
+// caller's pointers are there; `band`: {j0, j1} of a column band, or null.
+static int sw_check_args(const char *who, bool ptrs, const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw,
+                         int th, const int *band, size_t &ntw, size_t &nth) {
+    if (!ptrs || tw < 1 || th < 1 || tw > 16384) {
+        set_error(band ? "%s: invalid arguments" : "%s: invalid arguments (1 <= tw <= 16384, th >= 1)", who);
         return HCLIB_HIP_EINVAL;
     }
-    const size_t ntw = n1 / (size_t)tw, nth = n2 / (size_t)th;
-    if (ntw == 0 || nth == 0 || ntw * nth > 0x7fffffffull) {
-        set_error("hclib_hip_sw: empty or oversized tile grid");
+    ntw = n1 / (size_t)tw, nth = n2 / (size_t)th;
+    const bool grid = ntw != 0 && nth != 0 && ntw * nth <= 0x7fffffffull;
+    if (!grid || (band && (band[0] < 0 || band[1] <= band[0] || (size_t)band[1] > ntw))) {
+        if (band) set_error("%s: empty grid or band [%d, %d) outside 0..%zu", who, band[0], band[1], ntw);
+        else set_error("%s: empty or oversized tile grid", who);
         return HCLIB_HIP_EINVAL;
     }
     for (size_t k = 0; k < ntw * (size_t)tw; ++k)
-        if (s1[k] < 1 || s1[k] > 4) { set_error("hclib_hip_sw: s1 must be coded 1..4"); return HCLIB_HIP_EINVAL; }
+        if (s1[k] < 1 || s1[k] > 4) { set_error("%s: s1 must be coded 1..4", who); return HCLIB_HIP_EINVAL; }
     for (size_t k = 0; k < nth * (size_t)th; ++k)
-        if (s2[k] < 1 || s2[k] > 4) { set_error("hclib_hip_sw: s2 must be coded 1..4"); return HCLIB_HIP_EINVAL; }
-    HX_TRY(ensure_device());
-    Module &m = mod();
-    // schedule: "rows" (default) = owner-computes tile rows with granule
-    // hand-offs; "queue" = the generic DAG: dependency counters + ready list
-    const char *sched = getenv("HCLIB_HIP_SW_SCHED");
-    // the row schedule keeps two tile columns in LDS: wide tiles fall back
-    const size_t rows_lds = 2 * (size_t)(((tw + 1 + 3) & ~3) * 4) + 68 * 4 + 2 * (size_t)((tw + 3) & ~3) + 16 +
-                            2 * (size_t)(((th + 3) & ~3) * 4);
-    const bool dag = sched && !strcmp(sched, "dag");
-    const bool rows = !(sched && (!strcmp(sched, "queue") || dag)) && rows_lds <= 64 * 1024;
-    // multi-wave tile rows (th / 64 waves per workgroup) unless "rows1" asks
-    // for the one-wave-per-tile-row kernel
-    // multi-wave band form (sw_pick_form): the DAG's tile tasks default to two
-    // rows per lane (two waves per 256-row tile: one hand-off lag instead of
-    // three), the row schedule to four (one band per 256-row tile row: the
-    // per-row wavefront lag is paid once per 256 rows). SW-64K measured
-    // (profiles/r02/sw_forms.log): rows 12: 4.4 ms, 212: 3.55, 412: 3.50;
-    // dag 12: 11.2, 212: 9.4, 412: 9.6. Round 3, same box
-    // (profiles/r03/sw_forms_k64.log): hand-offs every 64 steps for the DAG's
-    // tiles, 212: 8.35 -> 214: 8.12-8.14 ms; rows 414 3.56 vs 412 3.49-3.51
-    const int form = sw_pick_form(th, dag ? 214 : 412), bh = sw_form_bh(form);
-    const bool band_shape = sw_band_ok(th, bh) && tw <= 65536;
-    const bool band = rows && band_shape && !(sched && !strcmp(sched, "rows1"));
-    // the promise DAG's 256-row tiles at most 512 wide: the packed-half body,
-    // tagged outputs (HCLIB_HIP_SW_PK=0: the band forms)
-    // (a two-sweep-wave body was exact but slower, 7.95 vs 6.56 ms, and was
-    // removed in round 5: DESIGN.md Appendix A)
-    const bool pk = dag && th == kSwPkTh && tw <= kSwPkMaxTw && env_int("HCLIB_HIP_SW_PK", 1) != 0;
-    const size_t nt = ntw * nth;
-    const size_t b_s1 = ntw * tw, b_s2 = nth * th;
-    const size_t b_bot = (rows || pk) ? 0 : nt * tw * 4, b_right = (rows || pk) ? 0 : nt * th * 4, b_c = nt * 4,
-                 b_dep = nt * 4, b_ready = nt * 4, b_gbot = (rows || pk) ? nt * tw * 8 : 0,
-                 b_gright = pk ? nt * th * 8 : 0, b_gc = pk ? nt * 8 : 0;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t total = al(b_s1) + al(b_s2) + al(b_bot) + al(b_right) + al(b_c) + al(b_dep) +
-                         al(b_ready) + al(b_gbot) + al(b_gright) + al(b_gc) + 1024;
-    DevBuf buf;
-    HX_TRY(buf.alloc(total, "hclib_hip_sw"));
-    char *d = buf.p;
-    SwCtx c;
-    size_t off = 0;
-    c.s1 = (const int8_t *)(d + off); off += al(b_s1);
-    c.s2 = (const int8_t *)(d + off); off += al(b_s2);
-    c.bottom = (int *)(d + off); off += al(b_bot);
-    c.right = (int *)(d + off); off += al(b_right);
-    c.corner = (int *)(d + off); off += al(b_c);
-    c.deps = (uint32_t *)(d + off); off += al(b_dep);
-    c.ready = (uint32_t *)(d + off); off += al(b_ready);
-    c.gbot = (unsigned long long *)(d + off); off += al(b_gbot);
-    c.gright = (unsigned long long *)(d + off); off += al(b_gright);
-    c.gcorner = (unsigned long long *)(d + off); off += al(b_gc);
-    uint32_t *misc = (uint32_t *)(d + off);
+        if (s2[k] < 1 || s2[k] > 4) { set_error("%s: s2 must be coded 1..4", who); return HCLIB_HIP_EINVAL; }
+    return HCLIB_HIP_OK;
+}
+
+// A zeroed c over one allocation `d` of p.bytes.total() bytes: its arrays and
+// counters, tile columns [j0, j1), every tile row. An array of no bytes gets
+// the next one's address (a band session's plain arrays, deps and ready alias
+// its granules): no kernel of a path touches an array the path does not have.
+static void sw_ctx(SwCtx &c, char *d, const SwPlan &p, const SwKnobs &kn, int tw, int th, size_t ntw, size_t nth, int j0,
+                   int j1) {
+    auto take = [&d](size_t bytes) { char *q = d; d += SwBytes::al(bytes); return q; };
+    c.s1 = (const int8_t *)take(p.bytes.s1);
+    c.s2 = (const int8_t *)take(p.bytes.s2);
+    c.bottom = (int *)take(p.bytes.bottom);
+    c.right = (int *)take(p.bytes.right);
+    c.corner = (int *)take(p.bytes.corner);
+    c.deps = (uint32_t *)take(p.bytes.deps);
+    c.ready = (uint32_t *)take(p.bytes.ready);
+    c.gbot = (unsigned long long *)take(p.bytes.gbot);
+    c.gright = (unsigned long long *)take(p.bytes.gright);
+    c.gcorner = (unsigned long long *)take(p.bytes.gcorner);
+    uint32_t *misc = (uint32_t *)take(SwBytes::kMisc);
     c.ready_tail = misc;
     c.ready_head = misc + 64;
     c.err = misc + 128;
@@ -1922,204 +1871,197 @@ static int sw_run(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int 
     c.ntw = (int)ntw;
     c.nth = (int)nth;
     c.spin_ms = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-    c.j0 = 0;
-    c.j1 = (int)ntw;
-    c.i0 = 0;
+    c.j0 = j0;
+    c.j1 = j1;
     c.i1 = (int)nth;
-    c.left_in = nullptr;
-    c.right_out = nullptr;
-    c.progressive = env_int("HCLIB_HIP_SW_PROGRESSIVE", 1);
-    c.dtrace = nullptr;
-    c.form = form;
-    c.bh = bh;
-    HX_HIP(hipMemcpyAsync((void *)c.s1, s1, b_s1, hipMemcpyHostToDevice, m.stream));
-    HX_HIP(hipMemcpyAsync((void *)c.s2, s2, b_s2, hipMemcpyHostToDevice, m.stream));
-    HX_HIP(hipMemsetAsync(misc, 0, 1024, m.stream));
-    {
-        uint32_t one = 1;  // tile 0 already sits at ready[0]
-        HX_HIP(hipMemcpyAsync(c.ready_tail, &one, 4, hipMemcpyHostToDevice, m.stream));
+    c.progressive = kn.progressive;
+    c.form = p.form;
+    c.bh = p.bh;
+}
+
+// the sequences, zeroed counters and tags, and the queue's first ready tile
+static int sw_upload(const SwPlan &p, const SwCtx &c, const int8_t *s1, const int8_t *s2, hipStream_t stream) {
+    HX_HIP(hipMemcpyAsync((void *)c.s1, s1, p.bytes.s1, hipMemcpyHostToDevice, stream));
+    HX_HIP(hipMemcpyAsync((void *)c.s2, s2, p.bytes.s2, hipMemcpyHostToDevice, stream));
+    HX_HIP(hipMemsetAsync(c.ready_tail, 0, SwBytes::kMisc, stream));
+    uint32_t one = 1;  // tile 0 already sits at ready[0]
+    HX_HIP(hipMemcpyAsync(c.ready_tail, &one, 4, hipMemcpyHostToDevice, stream));
+    // every granule's tag starts at 0 (not yet put); gcorner follows gright
+    if (p.bytes.gbot) HX_HIP(hipMemsetAsync(c.gbot, 0, p.bytes.gbot, stream));
+    if (p.bytes.gright) HX_HIP(hipMemsetAsync(c.gright, 0, SwBytes::al(p.bytes.gright) + p.bytes.gcorner, stream));
+    // deps / ready of every path that is not the row schedule
+    if (!p.rows()) hipLaunchKernelGGL(k_sw_init, dim3(1024), dim3(256), 0, stream, c.deps, c.ready, c.ntw, c.nth);
+    return HCLIB_HIP_OK;
+}
+
+// The plan's kernel on `grid` workgroups: (c), and on the DAG (c, *v); more
+// than 64 KiB of dynamic LDS has to be asked for, per kernel. The caller
+// looks at hipGetLastError.
+static void sw_launch(const SwPlan &p, int grid, hipStream_t stream, SwCtx &c, const DagView *v) {
+    static const void *const kernels[] = {  // in SwKernel's order
+        (const void *)k_sw,           (const void *)k_sw_dag,         (const void *)k_sw_dag_wg, (const void *)k_sw_dag_pk,
+        (const void *)k_sw_rows<true>, (const void *)k_sw_rows<false>, (const void *)k_sw_band_rows};
+    const void *kern = kernels[(int)p.kernel];
+    if (p.lds > 64 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds);
+    void *args[] = {&c, (void *)v};
+    (void)hipLaunchKernel(kern, dim3(grid), dim3(p.threads), args, p.lds, stream);
+}
+
+// the tile program's futures as a CSR over 3 promises per tile
+static void sw_tile_futures(size_t ntw, size_t nth, std::vector<uint32_t> &off, std::vector<uint32_t> &ids) {
+    const size_t nt = ntw * nth;
+    off.assign(nt + 1, 0);
+    ids.reserve(3 * nt);
+    for (size_t t = 0; t < nt; ++t) {
+        const size_t i = t / ntw, j = t % ntw;
+        if (j > 0) ids.push_back((uint32_t)(3 * (t - 1) + 0));
+        if (i > 0) ids.push_back((uint32_t)(3 * (t - ntw) + 1));
+        if (i > 0 && j > 0) ids.push_back((uint32_t)(3 * (t - ntw - 1) + 2));
+        off[t + 1] = (uint32_t)ids.size();
     }
-    if (rows || pk) {
-        // every granule's tag starts at 0 (not yet put)
-        HX_HIP(hipMemsetAsync(c.gbot, 0, b_gbot, m.stream));
-        if (pk) HX_HIP(hipMemsetAsync(c.gright, 0, al(b_gright) + b_gc, m.stream));
-    }
-    if (!rows) {
-        hipLaunchKernelGGL(k_sw_init, dim3(1024), dim3(256), 0, m.stream, c.deps, c.ready, c.ntw, c.nth);
-    }
-    const size_t lds = band ? sw_band_lds_bytes(th / bh)
-                            : 2 * (size_t)(((tw + 1 + 3) & ~3) * 4) + 68 * 4 + 2 * (size_t)((tw + 3) & ~3) + 16 +
-                                  (rows ? 2 * (size_t)(((th + 3) & ~3) * 4) : 0);
-    if (lds > 160 * 1024) {
-        set_error("hclib_hip_sw: tile too large for LDS");
-        return HCLIB_HIP_EINVAL;
-    }
-    int per_cu = (int)((160 * 1024) / lds);
-    // rows: one wave per CU owns tile rows (all resident, so every wait ends)
-    int wpc = env_int("HCLIB_HIP_SW_WAVES_PER_CU", rows ? 1 : 2);
-    if (wpc > per_cu) wpc = per_cu;
-    // the generic promise DAG launches at most 8 waves per CU
-    // (hclib_hip_dag_begin); clamp here rather than fail its argument check
-    if (dag && wpc > 8) wpc = 8;
-    if (wpc < 1) wpc = 1;
-    int grid = m.num_cus * wpc;
-    if (rows && grid > (int)nth) grid = (int)nth;
-    const void *kern = rows ? (c.progressive ? (const void *)k_sw_rows<true> : (const void *)k_sw_rows<false>)
-                            : (dag ? (const void *)k_sw_dag : (const void *)k_sw);
-    if (lds > 64 * 1024) (void)hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    hclib_hip_dag_stats_t dst{};
-    int path = 0;  // HCLIB_HIP_SW_PATH_* (reported by hclib_hip_sw_edges)
-    if (dag) {
-        // the tile program's futures as a CSR over 3 promises per tile
-        std::vector<uint32_t> off(nt + 1, 0), ids;
-        ids.reserve(3 * nt);
-        for (size_t t = 0; t < nt; ++t) {
-            const size_t i = t / ntw, j = t % ntw;
-            if (j > 0) ids.push_back((uint32_t)(3 * (t - 1) + 0));
-            if (i > 0) ids.push_back((uint32_t)(3 * (t - ntw) + 1));
-            if (i > 0 && j > 0) ids.push_back((uint32_t)(3 * (t - ntw - 1) + 2));
-            off[t + 1] = (uint32_t)ids.size();
-        }
-        // tile tasks on workgroups of th / 64 + 2 waves where the band
-        // kernel applies (HCLIB_HIP_SW_DAG_WAVE=1: one wave per tile)
-        const bool wg = band_shape && env_int("HCLIB_HIP_SW_DAG_WAVE", 0) == 0;
-        path = pk ? HCLIB_HIP_SW_PATH_DAG_PK : (wg ? HCLIB_HIP_SW_PATH_DAG_WG : HCLIB_HIP_SW_PATH_DAG_WAVE);
-        hclib_hip_dag_launch_t L;
-        HX_TRY(hclib_hip_dag_begin((uint32_t)nt, (uint32_t)(3 * nt), 0, nullptr, off.data(), ids.data(), nullptr,
-                                   nullptr, pk ? env_int("HCLIB_HIP_SW_PK_WGS_PER_CU", 1)
-                                               : (wg ? env_int("HCLIB_HIP_SW_DAG_WGS_PER_CU", 1) : wpc),
-                                   c.spin_ms, &L));
-        if (pk) {
-            const size_t plds = sw_pk_lds_bytes(tw);
-            c.dtrace = ((const DagView *)L.view)->trace;
-            if (plds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_sw_dag_pk,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)plds);
-            hipLaunchKernelGGL(k_sw_dag_pk, dim3(L.grid), dim3(192), plds, m.stream, c, *(const DagView *)L.view);
-        } else if (wg) {
-            const size_t blds = sw_band_lds_bytes(th / bh) + (4 + 2 * (size_t)th) * 4;  // + kept right columns
-            if (blds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_sw_dag_wg,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-            c.dtrace = ((const DagView *)L.view)->trace;
-            hipLaunchKernelGGL(k_sw_dag_wg, dim3(L.grid), dim3(64 * (th / bh) + 128), blds, m.stream, c,
-                               *(const DagView *)L.view);
-        } else {
-            hipLaunchKernelGGL(k_sw_dag, dim3(L.grid), dim3(64), lds, m.stream, c, *(const DagView *)L.view);
-        }
-        // (the packed body's tagged puts are checked for double puts here)
-        std::vector<uint8_t> sat(pk ? 3 * nt : 0);
-        HX_TRY(hclib_hip_dag_end("hclib_hip_sw (dag)", nullptr, pk ? sat.data() : nullptr, &dst));
-    } else {
-        path = band ? HCLIB_HIP_SW_PATH_BAND_ROWS : (rows ? HCLIB_HIP_SW_PATH_ROWS1 : HCLIB_HIP_SW_PATH_QUEUE);
+}
+
+// The whole grid, timed: between the module's events, or on the generic
+// promise DAG (hclib_hip_dag_begin / _end), which times it and counts its tasks.
+static int sw_launch_timed(const SwPlan &p, SwCtx &c, Module &m, hclib_hip_dag_stats_t *dst) {
+    if (!p.dag()) {
         HX_HIP(hipEventRecord(m.ev0, m.stream));
-        if (band) {
-            const int k = sw_band_rows_per_wg(th, bh), nblk = ((int)nth + k - 1) / k;
-            const int g = nblk < m.num_cus ? nblk : m.num_cus;
-            const size_t blds = sw_band_lds_bytes(k * (th / bh));
-            if (blds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_sw_band_rows,
-                                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-            hipLaunchKernelGGL(k_sw_band_rows, dim3(g), dim3(64 * k * (th / bh) + 128), blds, m.stream, c);
-        } else if (rows && c.progressive) hipLaunchKernelGGL(k_sw_rows<true>, dim3(grid), dim3(64), lds, m.stream, c);
-        else if (rows) hipLaunchKernelGGL(k_sw_rows<false>, dim3(grid), dim3(64), lds, m.stream, c);
-        else hipLaunchKernelGGL(k_sw, dim3(grid), dim3(64), lds, m.stream, c);
+        sw_launch(p, p.grid, m.stream, c, nullptr);  // rows: c covers every tile row, p.grid = rows_grid(nth)
         HX_HIP(hipGetLastError());
-        HX_HIP(hipEventRecord(m.ev1, m.stream));
+        return hip_check(hipEventRecord(m.ev1, m.stream), "hipEventRecord(m.ev1, m.stream)");
     }
-    uint32_t herr = 0;
-    unsigned long long st[10] = {0};
-    int corner = 0;
-    HX_HIP(hipStreamSynchronize(m.stream));
-    (void)hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost);
-    (void)hipMemcpy(st, c.stats, sizeof(st), hipMemcpyDeviceToHost);
-    if (HX_STAMPS && (band || (dag && band_shape))) {
+    const size_t nt = (size_t)c.ntw * c.nth;
+    std::vector<uint32_t> off, ids;
+    sw_tile_futures((size_t)c.ntw, (size_t)c.nth, off, ids);
+    hclib_hip_dag_launch_t L;
+    HX_TRY(hclib_hip_dag_begin((uint32_t)nt, (uint32_t)(3 * nt), 0, nullptr, off.data(), ids.data(), nullptr, nullptr,
+                               p.wgs_per_cu, c.spin_ms, &L));
+    // the workgroup tile tasks' stamps (diagnostic builds)
+    if (p.kernel != SwKernel::DagWave) c.dtrace = ((const DagView *)L.view)->trace;
+    sw_launch(p, L.grid, m.stream, c, (const DagView *)L.view);
+    // (the packed body's tagged puts are checked for double puts here)
+    std::vector<uint8_t> sat(p.pk() ? 3 * nt : 0);
+    return hclib_hip_dag_end("hclib_hip_sw (dag)", nullptr, p.pk() ? sat.data() : nullptr, dst);
+}
+
+// diagnostic build: the phases' cycles that the kernels left in c.stats
+static void sw_print_stamps(const SwPlan &p, const SwCtx &c, const unsigned long long *st) {
+    const size_t nth = (size_t)c.nth;
+    if (HX_STAMPS && (p.path == HCLIB_HIP_SW_PATH_BAND_ROWS || (p.dag() && sw_band_ok(c.th, c.bh)))) {
         unsigned long long t[29] = {0};
         (void)hipMemcpy(t, c.stats, sizeof(t), hipMemcpyDeviceToHost);
-        const double per = dag ? (double)nt : (double)nth;  // per tile (DAG) or per tile row
-        for (int w = 0; w < 3 && w < th / bh; ++w)
+        const double per = p.dag() ? (double)c.ntw * nth : (double)nth;  // per tile (DAG) or per tile row
+        for (int w = 0; w < 3 && w < c.th / c.bh; ++w)
             fprintf(stderr, "sw band wave %d phases (cycles per %s): compute %.0f wait-top %.0f chunk-top %.0f"
                             " publish %.0f prologue %.0f\n",
-                    w, dag ? "tile" : "row", (double)t[4 + 6 * w] / per, (double)t[5 + 6 * w] / per,
+                    w, p.dag() ? "tile" : "row", (double)t[4 + 6 * w] / per, (double)t[5 + 6 * w] / per,
                     (double)t[6 + 6 * w] / per, (double)t[7 + 6 * w] / per, (double)t[8 + 6 * w] / per);
-        if (!dag)
+        if (!p.dag())
             fprintf(stderr, "sw band: row start spacing %.3f us, last row %.3f us\n",
                     nth > 1 ? (double)(t[26] - t[27]) * 0.01 / (double)(nth - 1) : 0.0, (double)(t[28] - t[26]) * 0.01);
     } else if (HX_STAMPS && st[0])
         fprintf(stderr, "sw phases (cycles/tile): inputs %.0f band-setup %.0f ramp-in %.0f steady %.0f ramp-out %.0f outputs %.0f\n",
                 (double)st[4] / st[0], (double)st[5] / st[0], (double)st[6] / st[0], (double)st[7] / st[0],
                 (double)st[8] / st[0], (double)st[9] / st[0]);
-    if (rows) {
-        unsigned long long g = 0;  // bottom_row[tw-1] of the last tile (its granule)
-        (void)hipMemcpy(&g, c.gbot + (nt * tw - 1), 8, hipMemcpyDeviceToHost);
-        corner = (int)(uint32_t)g;
-        // the edges the row schedule resolved: each tile's up, left and
-        // diagonal futures (the same 3-per-interior-tile count as the queue)
-        st[1] = 3ull * (ntw - 1) * (nth - 1) + (ntw - 1) + (nth - 1);
-    } else if (pk) {
-        unsigned long long g = 0;  // the last tile's corner granule
-        (void)hipMemcpy(&g, c.gcorner + (nt - 1), 8, hipMemcpyDeviceToHost);
-        corner = (int)(uint32_t)g;
+}
+
+// H of the matrix's last cell, from wherever the path left it
+static int sw_read_score(const SwPlan &p, const SwCtx &c) {
+    const size_t nt = (size_t)c.ntw * c.nth;
+    unsigned long long g = 0;  // rows: bottom_row[tw-1] of the last tile (its granule); packed: its corner granule
+    int corner = 0;
+    if (p.rows()) (void)hipMemcpy(&g, c.gbot + (nt * c.tw - 1), 8, hipMemcpyDeviceToHost);
+    else if (p.pk()) (void)hipMemcpy(&g, c.gcorner + (nt - 1), 8, hipMemcpyDeviceToHost);
+    else (void)hipMemcpy(&corner, c.corner + (nt - 1), 4, hipMemcpyDeviceToHost);
+    return p.rows() || p.pk() ? (int)(uint32_t)g : corner;
+}
+
+// What each schedule leaves on the device (include/hclib_hip.h), to the
+// host: granules (rows, packed) or the reference's plain arrays.
+static int sw_read_edges(const SwPlan &p, const SwCtx &c, hclib_hip_sw_edges_t *edges, uint32_t *filled) {
+    const char *who = "hclib_hip_sw_edges";
+    const size_t nt = (size_t)c.ntw * c.nth, per = (size_t)c.tw;
+    auto tile_tw = [per](size_t k) { return k / per; };
+    uint32_t have = 0;
+    edges->path = p.path;
+    edges->form = (p.path == HCLIB_HIP_SW_PATH_BAND_ROWS || p.path == HCLIB_HIP_SW_PATH_DAG_WG) ? p.form : 0;
+    if (p.rows() || p.pk()) {
+        // a band workgroup of several tile rows publishes only its last one
+        const bool all_rows = p.rows_per_wg == 1;
+        int *cn = (p.rows() && all_rows) ? edges->corners : nullptr;  // rows: the bottom row's last value
+        if (all_rows && (edges->bottoms || cn)) {
+            HX_TRY(sw_untag(who, "bottom-row", c.gbot, nt * per, 1, 0, per, tile_tw, edges->bottoms, cn));
+            if (edges->bottoms) have |= HCLIB_HIP_SW_EDGE_BOTTOMS;
+            if (cn) have |= HCLIB_HIP_SW_EDGE_CORNERS;
+        }
+        if (p.pk() && edges->rights) {
+            const size_t ph = (size_t)c.th;
+            HX_TRY(sw_untag(who, "right-column", c.gright, nt * ph, 1, 0, ph,
+                            [ph](size_t k) { return k / ph; }, edges->rights, nullptr));
+            have |= HCLIB_HIP_SW_EDGE_RIGHTS;
+        }
+        if (p.pk() && edges->corners) {
+            HX_TRY(sw_untag(who, "corner", c.gcorner, nt, 1, 0, 1, [](size_t k) { return k; }, edges->corners,
+                            nullptr));
+            have |= HCLIB_HIP_SW_EDGE_CORNERS;
+        }
     } else {
-        (void)hipMemcpy(&corner, c.corner + (nt - 1), 4, hipMemcpyDeviceToHost);
+        int *const host[3] = {edges->bottoms, edges->rights, edges->corners};  // HCLIB_HIP_SW_EDGE_* = 1 << k
+        const int *const dev[3] = {c.bottom, c.right, c.corner};
+        const size_t bytes[3] = {p.bytes.bottom, p.bytes.right, p.bytes.corner};
+        for (int k = 0; k < 3; ++k)
+            if (host[k]) {
+                HX_HIP(hipMemcpy(host[k], dev[k], bytes[k], hipMemcpyDeviceToHost));
+                have |= 1u << k;
+            }
     }
-    if (dag) {  // the DAG's own counters: tasks run, and every future resolved
-        st[0] = dst.tasks;
-        st[1] = 3ull * (ntw - 1) * (nth - 1) + (ntw - 1) + (nth - 1);
+    if (filled) *filled = have;
+    return HCLIB_HIP_OK;
+}
+
+// hclib_hip_sw and hclib_hip_sw_edges: one body. `edges` null is
+// hclib_hip_sw as it always was; otherwise the tiles' outputs are copied to
+// the host after the run's synchronise and its checks.
+static int sw_run(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th, int *score,
+                  hclib_hip_sw_result_t *result, hclib_hip_sw_edges_t *edges, uint32_t *filled) {
+    if (filled) *filled = 0;
+    size_t ntw = 0, nth = 0;
+    HX_TRY(sw_check_args("hclib_hip_sw", s1 && s2 && score, s1, n1, s2, n2, tw, th, nullptr, ntw, nth));
+    HX_TRY(ensure_device());
+    Module &m = mod();
+    const SwKnobs kn = sw_knobs();
+    const SwPlan p = sw_plan(tw, th, ntw, nth, m.num_cus, kn);
+    if (p.too_large) {
+        set_error("hclib_hip_sw: tile too large for LDS");
+        return HCLIB_HIP_EINVAL;
     }
+    DevBuf buf;
+    HX_TRY(buf.alloc(p.bytes.total(), "hclib_hip_sw"));
+    SwCtx c{};
+    sw_ctx(c, buf.p, p, kn, tw, th, ntw, nth, 0, (int)ntw);
+    HX_TRY(sw_upload(p, c, s1, s2, m.stream));
+    hclib_hip_dag_stats_t dst{};
+    HX_TRY(sw_launch_timed(p, c, m, &dst));
+
+    const size_t nt = ntw * nth;
+    unsigned long long st[10] = {0};
+    HX_HIP(hipStreamSynchronize(m.stream));
+    (void)hipMemcpy(st, c.stats, sizeof(st), hipMemcpyDeviceToHost);
+    sw_print_stamps(p, c, st);
+    // the queue counts its releases on the device. Rows and DAG resolve each
+    // tile's up, left and diagonal futures (the same 3-per-interior-tile
+    // count); the DAG counts the tasks it ran itself
+    if (p.rows() || p.dag()) st[1] = 3ull * (ntw - 1) * (nth - 1) + (ntw - 1) + (nth - 1);
+    if (p.dag()) st[0] = dst.tasks;
     float ms = 0;
     (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
-    if (herr) {
-        set_error("hclib_hip_sw: device error %u", herr);
-        return HCLIB_HIP_EDEVICE;
-    }
+    HX_TRY(sw_device_error("hclib_hip_sw", c));
     if (st[0] != nt) {
         set_error("hclib_hip_sw: executed %llu of %zu tiles", st[0], nt);
         return HCLIB_HIP_EDEVICE;
     }
-    if (edges) {
-        // what each schedule leaves on the device (include/hclib_hip.h):
-        // granules (rows, packed) or the reference's plain arrays
-        const char *who = "hclib_hip_sw_edges";
-        const size_t per = (size_t)tw;
-        auto tile_tw = [per](size_t k) { return k / per; };
-        uint32_t have = 0;
-        edges->path = path;
-        edges->form = (band || path == HCLIB_HIP_SW_PATH_DAG_WG) ? form : 0;
-        if (rows || pk) {
-            // a band workgroup of several tile rows publishes only its last one
-            const bool all_rows = !(band && sw_band_rows_per_wg(th, bh) > 1);
-            int *cn = (rows && all_rows) ? edges->corners : nullptr;  // rows: the bottom row's last value
-            if (all_rows && (edges->bottoms || cn)) {
-                HX_TRY(sw_untag(who, "bottom-row", c.gbot, nt * per, 1, 0, per, tile_tw, edges->bottoms, cn));
-                if (edges->bottoms) have |= HCLIB_HIP_SW_EDGE_BOTTOMS;
-                if (cn) have |= HCLIB_HIP_SW_EDGE_CORNERS;
-            }
-            if (pk && edges->rights) {
-                const size_t ph = (size_t)th;
-                HX_TRY(sw_untag(who, "right-column", c.gright, nt * ph, 1, 0, ph,
-                                [ph](size_t k) { return k / ph; }, edges->rights, nullptr));
-                have |= HCLIB_HIP_SW_EDGE_RIGHTS;
-            }
-            if (pk && edges->corners) {
-                HX_TRY(sw_untag(who, "corner", c.gcorner, nt, 1, 0, 1, [](size_t k) { return k; }, edges->corners,
-                                nullptr));
-                have |= HCLIB_HIP_SW_EDGE_CORNERS;
-            }
-        } else {
-            if (edges->bottoms) {
-                HX_HIP(hipMemcpy(edges->bottoms, c.bottom, b_bot, hipMemcpyDeviceToHost));
-                have |= HCLIB_HIP_SW_EDGE_BOTTOMS;
-            }
-            if (edges->rights) {
-                HX_HIP(hipMemcpy(edges->rights, c.right, b_right, hipMemcpyDeviceToHost));
-                have |= HCLIB_HIP_SW_EDGE_RIGHTS;
-            }
-            if (edges->corners) {
-                HX_HIP(hipMemcpy(edges->corners, c.corner, b_c, hipMemcpyDeviceToHost));
-                have |= HCLIB_HIP_SW_EDGE_CORNERS;
-            }
-        }
-        if (filled) *filled = have;
-    }
-    *score = corner;  // bottom_row[tw-1] of the last tile == its corner (:239)
+    if (edges) HX_TRY(sw_read_edges(p, c, edges, filled));
+    *score = sw_read_score(p, c);  // bottom_row[tw-1] of the last tile == its corner (:239)
     if (result) {
         result->tiles = st[0];
         result->releases = st[1];
@@ -2156,71 +2098,33 @@ extern "C" int hclib_hip_sw_edges(const int8_t *s1, size_t n1, const int8_t *s2,
 // on the device across blocks, so a block only needs its left column.
 struct hclib_hip_sw_band {
     SwCtx c;
+    SwPlan p;  // planned once, when the session begins
     char *mem;
-    size_t lds;
-    int grid_cap;
 };
 
 extern "C" int hclib_hip_sw_band_begin(const int8_t *s1, size_t n1, const int8_t *s2, size_t n2, int tw, int th,
                                        int j0, int j1, hclib_hip_sw_band_t **out) {
-    if (!out || !s1 || !s2 || tw < 1 || th < 1 || tw > 16384) {
-        set_error("hclib_hip_sw_band_begin: invalid arguments");
-        return HCLIB_HIP_EINVAL;
-    }
-    *out = nullptr;
-    const size_t ntw = n1 / (size_t)tw, nth = n2 / (size_t)th;
-    if (ntw == 0 || nth == 0 || ntw * nth > 0x7fffffffull || j0 < 0 || j1 <= j0 || (size_t)j1 > ntw) {
-        set_error("hclib_hip_sw_band_begin: empty grid or band [%d, %d) outside 0..%zu", j0, j1, ntw);
-        return HCLIB_HIP_EINVAL;
-    }
-    for (size_t k = 0; k < ntw * (size_t)tw; ++k)
-        if (s1[k] < 1 || s1[k] > 4) { set_error("hclib_hip_sw_band_begin: s1 must be coded 1..4"); return HCLIB_HIP_EINVAL; }
-    for (size_t k = 0; k < nth * (size_t)th; ++k)
-        if (s2[k] < 1 || s2[k] > 4) { set_error("hclib_hip_sw_band_begin: s2 must be coded 1..4"); return HCLIB_HIP_EINVAL; }
-    const size_t lds = 2 * (size_t)(((tw + 1 + 3) & ~3) * 4) + 68 * 4 + 2 * (size_t)((tw + 3) & ~3) + 16 +
-                       2 * (size_t)(((th + 3) & ~3) * 4);
-    if (lds > 64 * 1024) {
+    const int band[2] = {j0, j1};
+    size_t ntw = 0, nth = 0;
+    if (out) *out = nullptr;
+    HX_TRY(sw_check_args("hclib_hip_sw_band_begin", out && s1 && s2, s1, n1, s2, n2, tw, th, band, ntw, nth));
+    if (sw_tile_lds_bytes(tw, th, true) > 64 * 1024) {
         set_error("hclib_hip_sw_band_begin: tile too large for the row schedule");
         return HCLIB_HIP_EINVAL;
     }
     HX_TRY(ensure_device());
-    Module &m = mod();
-    const size_t nt = ntw * nth, b_s1 = ntw * tw, b_s2 = nth * th, b_gbot = nt * tw * 8;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t total = al(b_s1) + al(b_s2) + al(b_gbot) + 1024;
+    const SwKnobs kn = sw_knobs();
     hclib_hip_sw_band *h = new hclib_hip_sw_band();
-    if (hipMalloc((void **)&h->mem, total) != hipSuccess) {
+    const SwPlan &p = h->p = sw_plan(tw, th, ntw, nth, mod().num_cus, kn, true);
+    if (hipMalloc((void **)&h->mem, p.bytes.total()) != hipSuccess) {
+        set_error("hclib_hip_sw_band_begin: hipMalloc(%zu) failed", p.bytes.total());
         delete h;
-        set_error("hclib_hip_sw_band_begin: hipMalloc(%zu) failed", total);
         return HCLIB_HIP_ENOMEM;
     }
-    SwCtx &c = h->c;
-    memset(&c, 0, sizeof(c));
-    size_t off = 0;
-    c.s1 = (const int8_t *)(h->mem + off); off += al(b_s1);
-    c.s2 = (const int8_t *)(h->mem + off); off += al(b_s2);
-    c.gbot = (unsigned long long *)(h->mem + off); off += al(b_gbot);
-    uint32_t *misc = (uint32_t *)(h->mem + off);
-    c.err = misc + 128;
-    c.stats = (unsigned long long *)(misc + 192);
-    c.tw = tw;
-    c.th = th;
-    c.ntw = (int)ntw;
-    c.nth = (int)nth;
-    c.j0 = j0;
-    c.j1 = j1;
-    c.progressive = env_int("HCLIB_HIP_SW_PROGRESSIVE", 1);
-    c.dtrace = nullptr;
-    c.form = sw_pick_form(th, 412);
-    c.bh = sw_form_bh(c.form);
-    c.spin_ms = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-    h->lds = lds;
-    h->grid_cap = m.num_cus;
-    int rc;
-    if ((rc = hip_check(hipMemcpy((void *)c.s1, s1, b_s1, hipMemcpyHostToDevice), "copy s1")) ||
-        (rc = hip_check(hipMemcpy((void *)c.s2, s2, b_s2, hipMemcpyHostToDevice), "copy s2")) ||
-        (rc = hip_check(hipMemset(misc, 0, 1024), "memset")) ||
-        (rc = hip_check(hipMemset(c.gbot, 0, b_gbot), "memset granules"))) {
+    sw_ctx(h->c, h->mem, p, kn, tw, th, ntw, nth, j0, j1);
+    int rc = sw_upload(p, h->c, s1, s2, nullptr);  // the session has no stream of its own yet
+    if (!rc) rc = hip_check(hipStreamSynchronize(nullptr), "upload");
+    if (rc) {
         (void)hipFree(h->mem);
         delete h;
         return rc;
@@ -2236,27 +2140,15 @@ extern "C" int hclib_hip_sw_band_rows(hclib_hip_sw_band_t *h, int i0, int i1, co
                   left_in ? "given" : "missing");
         return HCLIB_HIP_EINVAL;
     }
+    // one wave owns each tile row (or a workgroup rows_per_wg of them); at most
+    // grid_cap workgroups, so every one is resident and each granule wait ends
+    // (rows above i0 finished in an earlier launch)
     SwCtx c = h->c;
     c.i0 = i0;
     c.i1 = i1;
     c.left_in = left_in;
     c.right_out = right_out;
-    // one wave owns each tile row; every wave of the block is resident, so
-    // each granule wait ends (rows above i0 finished in an earlier launch)
-    int grid = i1 - i0;
-    if (grid > h->grid_cap) grid = h->grid_cap;
-    const char *sched = getenv("HCLIB_HIP_SW_SCHED");
-    if (sw_band_ok(c.th, c.bh) && !(sched && !strcmp(sched, "rows1"))) {
-        const int k = sw_band_rows_per_wg(c.th, c.bh), nblk = (i1 - i0 + k - 1) / k;
-        const int g = nblk < h->grid_cap ? nblk : h->grid_cap;
-        const size_t blds = sw_band_lds_bytes(k * (c.th / c.bh));
-        if (blds > 64 * 1024) (void)hipFuncSetAttribute((const void *)k_sw_band_rows,
-                                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)blds);
-        hipLaunchKernelGGL(k_sw_band_rows, dim3(g), dim3(64 * k * (c.th / c.bh) + 128), blds, (hipStream_t)stream,
-                           c);
-    }
-    else if (c.progressive) hipLaunchKernelGGL(k_sw_rows<true>, dim3(grid), dim3(64), h->lds, (hipStream_t)stream, c);
-    else hipLaunchKernelGGL(k_sw_rows<false>, dim3(grid), dim3(64), h->lds, (hipStream_t)stream, c);
+    sw_launch(h->p, h->p.rows_grid(i1 - i0), (hipStream_t)stream, c, nullptr);
     return hip_check(hipGetLastError(), "k_sw_rows (band) launch");
 }
 
@@ -2267,12 +2159,7 @@ extern "C" int hclib_hip_sw_band_bottoms(hclib_hip_sw_band_t *h, void *stream, i
     }
     HX_TRY(hip_check(hipStreamSynchronize((hipStream_t)stream), "k_sw_rows (band)"));
     const SwCtx &c = h->c;
-    uint32_t herr = 0;
-    HX_HIP(hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost));
-    if (herr) {
-        set_error("hclib_hip_sw_band_bottoms: device error %u", herr);
-        return HCLIB_HIP_EDEVICE;
-    }
+    HX_TRY(sw_device_error("hclib_hip_sw_band_bottoms", c));
     const size_t per = (size_t)c.tw, w = (size_t)(c.j1 - c.j0) * per, ntw = (size_t)c.ntw, j0 = (size_t)c.j0;
     return sw_untag("hclib_hip_sw_band_bottoms", "bottom-row", c.gbot + j0 * per, (size_t)c.nth * w, (size_t)c.nth,
                     ntw * per, per, [=](size_t k) { return (k / w) * ntw + j0 + (k % w) / per; }, out, nullptr);
@@ -2284,11 +2171,10 @@ extern "C" int hclib_hip_sw_band_end(hclib_hip_sw_band_t *h, void *stream, int *
         return HCLIB_HIP_EINVAL;
     }
     int rc = hip_check(hipStreamSynchronize((hipStream_t)stream), "k_sw_rows (band)");
-    uint32_t herr = 0;
     unsigned long long st[4] = {0}, g = 0;
     const SwCtx &c = h->c;
     if (!rc) {
-        (void)hipMemcpy(&herr, c.err, 4, hipMemcpyDeviceToHost);
+        rc = sw_device_error("hclib_hip_sw_band_end", c);
         (void)hipMemcpy(st, c.stats, sizeof(st), hipMemcpyDeviceToHost);
         // bottom-right cell of the band's last tile (the score for the last band)
         const size_t t = (size_t)(c.nth - 1) * c.ntw + (c.j1 - 1);
@@ -2297,10 +2183,6 @@ extern "C" int hclib_hip_sw_band_end(hclib_hip_sw_band_t *h, void *stream, int *
     (void)hipFree(h->mem);
     delete h;
     if (rc) return rc;
-    if (herr) {
-        set_error("hclib_hip_sw_band_end: device error %u", herr);
-        return HCLIB_HIP_EDEVICE;
-    }
     if ((g >> 32) != 1ull) {
         set_error("hclib_hip_sw_band_end: the band's last tile was never computed (rows missing)");
         return HCLIB_HIP_EDEVICE;

@@ -126,7 +126,8 @@ def test_one_wave_tile_rows(shape, progressive, monkeypatch):
 # ----------------------------------------------------- multi-wave band rows
 def _form_for(form, th):
     """sw_pick_form's fallback: four rows per lane need th % 256 == 0, two
-    th % 128 == 0; else the same skew and hand-off with fewer rows."""
+    th % 128 == 0; else the same skew and hand-off with fewer rows (the C++
+    rule itself is checked without a GPU by tests/test_sw_plan.py)."""
     if form > 400 and th % 256:
         form -= 200
     if form > 200 and th % 128:
