@@ -187,6 +187,35 @@ class FloorplanResult(C.Structure):
                                           "chunks_stolen")] + [("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
 
 
+class AlignmentInput(C.Structure):
+    """hclib_hip_alignment_input_t."""
+
+    _fields_ = [("nseqs", C.c_int32), ("total", C.c_int32), ("length", C.POINTER(C.c_int32)),
+                ("offset", C.POINTER(C.c_int32)), ("codes", C.POINTER(C.c_uint8)), ("names", C.c_void_p)]
+
+
+class AlignmentMatrix(C.Structure):
+    """hclib_hip_alignment_matrix_t."""
+
+    _fields_ = [("avscore", C.c_int32), ("score", C.c_int32 * 32 * 32)]
+
+
+class AlignmentPair(C.Structure):
+    """hclib_hip_alignment_pair_t."""
+
+    _fields_ = [(k, C.c_int32) for k in ("si", "sj", "g", "gh", "maxscore", "se1", "se2", "sb1", "sb2", "matches",
+                                         "diff_calls", "type2", "ties")]
+
+
+class AlignmentResult(C.Structure):
+    """hclib_hip_alignment_result_t."""
+
+    _fields_ = [("scores", C.c_void_p)] + \
+               [(k, C.c_uint64) for k in ("pairs", "tasks", "created", "promises", "pair_tasks", "spawn_tasks",
+                                          "leaf_tasks", "matches", "diff_calls", "type2", "ties", "cells")] + \
+               [("cutoff", C.c_int32), ("kernel_ms", C.c_double), ("cells_per_s", C.c_double)]
+
+
 class AtomicViewStruct(C.Structure):
     """hclib_hip_atomic_view_t: what device code is handed for one atomic."""
 
@@ -213,6 +242,8 @@ EXPORTS_HIP = [
     "hclib_hip_strassen", "hclib_hip_strassen_bounds", "hclib_hip_strassen_last_ticks",
     "hclib_hip_health", "hclib_hip_health_bounds", "hclib_hip_health_last_ticks",
     "hclib_hip_floorplan", "hclib_hip_floorplan_read_input",
+    "hclib_hip_alignment", "hclib_hip_alignment_read_input", "hclib_hip_alignment_free_input",
+    "hclib_hip_alignment_read_matrix", "hclib_hip_alignment_bounds", "hclib_hip_alignment_last_ticks",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -309,6 +340,15 @@ def lib():
         L.hclib_hip_health_bounds.argtypes = [C.POINTER(HealthParams), C.POINTER(C.c_uint64)]
         L.hclib_hip_health_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
         L.hclib_hip_health_last_ticks.restype = None
+        L.hclib_hip_alignment.argtypes = [C.POINTER(AlignmentInput), C.POINTER(AlignmentMatrix), C.c_int,
+                                          C.POINTER(AlignmentResult), C.c_void_p]
+        L.hclib_hip_alignment_read_input.argtypes = [C.c_char_p, C.POINTER(AlignmentInput)]
+        L.hclib_hip_alignment_free_input.argtypes = [C.POINTER(AlignmentInput)]
+        L.hclib_hip_alignment_free_input.restype = None
+        L.hclib_hip_alignment_read_matrix.argtypes = [C.c_char_p, C.POINTER(AlignmentMatrix)]
+        L.hclib_hip_alignment_bounds.argtypes = [C.POINTER(AlignmentInput), C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_alignment_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_alignment_last_ticks.restype = None
         _lib = L
     return _lib
 
@@ -1081,6 +1121,115 @@ def floorplan(cells_or_path, prune: bool = True, hist: bool = False) -> dict:
     if hist:
         out["hist"] = list(h)[:inp.n + 1]
     return out
+
+
+# ------------------------------------------------------------ BOTS alignment
+ALIGNMENT_CODES = "ABCDEFGHIKLMNPQRSTUVWXYZ-"  # a residue's code is its index; '-' is stored as 31
+ALIGNMENT_MAX_LEN = 4999
+ALIGNMENT_DEFAULT_CUTOFF = 16384
+ALIGNMENT_BOUNDS = ("pairs", "tasks", "spawns", "diff_calls", "arena_bytes", "row_bytes")
+ALIGNMENT_TICKS = ("root", "pair", "spawn", "leaf")
+
+
+def alignment_read_input(path):
+    """A BOTS alignment input (a Pearson file with the `Number of sequences is
+    <n>` line) through hclib_hip_alignment_read_input, on the host alone:
+    [(name, codes)], codes a list of residue codes as the reference's readseqs
+    leaves them."""
+    inp = AlignmentInput()
+    _check(lib().hclib_hip_alignment_read_input(os.fsencode(path), C.byref(inp)), "hclib_hip_alignment_read_input")
+    try:
+        names = C.string_at(inp.names, inp.nseqs * 31)
+        return [(names[31 * i:31 * i + 31].split(b"\0")[0].decode("latin-1"),
+                 [inp.codes[inp.offset[i] + k] for k in range(inp.length[i])]) for i in range(inp.nseqs)]
+    finally:
+        lib().hclib_hip_alignment_free_input(C.byref(inp))
+
+
+def alignment_read_matrix(path):
+    """A substitution-matrix file through
+    hclib_hip_alignment_read_matrix: (avscore, 32 rows of 32 scores)."""
+    m = AlignmentMatrix()
+    _check(lib().hclib_hip_alignment_read_matrix(os.fsencode(path), C.byref(m)), "hclib_hip_alignment_read_matrix")
+    return m.avscore, [list(row) for row in m.score]
+
+
+def _alignment_input(seqs):
+    """(AlignmentInput, the arrays it points into) of [(name, codes)], [codes] or an input file."""
+    if isinstance(seqs, (str, bytes, os.PathLike)):
+        seqs = alignment_read_input(seqs)
+    codes = [list(q[1]) if isinstance(q, tuple) else list(q) for q in seqs]
+    if any(not 0 <= c <= 255 for q in codes for c in q):
+        raise ValueError("alignment: residue codes are 0..31")
+    n, total = len(codes), sum(len(q) for q in codes)
+    length = (C.c_int32 * max(n, 1))(*[len(q) for q in codes])
+    offset = (C.c_int32 * max(n, 1))()
+    flat = (C.c_uint8 * max(total, 1))()
+    at = 0
+    for i, q in enumerate(codes):
+        offset[i] = at
+        flat[at:at + len(q)] = q
+        at += len(q)
+    inp = AlignmentInput(nseqs=n, total=total, length=length, offset=offset, codes=flat, names=None)
+    return inp, (length, offset, flat)
+
+
+def _alignment_matrix(matrix) -> AlignmentMatrix:
+    if isinstance(matrix, AlignmentMatrix):
+        return matrix
+    if isinstance(matrix, (str, bytes, os.PathLike)):
+        matrix = alignment_read_matrix(matrix)
+    avscore, rows = matrix
+    if len(rows) != 32 or any(len(r) != 32 for r in rows):
+        raise ValueError("alignment: the matrix has 32 x 32 scores")
+    m = AlignmentMatrix(avscore=avscore)
+    for i, row in enumerate(rows):
+        for j, v in enumerate(row):
+            m.score[i][j] = v
+    return m
+
+
+def alignment_bounds(seqs, cutoff: int = 0) -> dict:
+    """What an alignment() of these sequences uses at most
+    (hclib_hip_alignment_bounds), on the host alone: ALIGNMENT_BOUNDS."""
+    inp, keep = _alignment_input(seqs)
+    out = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_alignment_bounds(C.byref(inp), cutoff, out), "hclib_hip_alignment_bounds")
+    return dict(zip(ALIGNMENT_BOUNDS, out))
+
+
+def alignment(seqs, matrix, cutoff: int = 0, pairs: bool = False) -> dict:
+    """BOTS alignment on dynamic device dataflow (hclib_hip_alignment): every
+    pair of the sequences aligned by Myers-Miller with affine gaps in one
+    launch, a task per pair and two per diff of more than `cutoff` cells (0:
+    the default). seqs: an input file, [(name, codes)] or [codes]; matrix: a
+    matrix file or (avscore, rows). Returns the fields of
+    hclib_hip_alignment_result_t with "scores" the nseqs x nseqs matrix the
+    reference prints (a list of rows) and, with pairs, a dict per pair
+    by the names of hclib_hip_alignment_pair_t
+    ("pair_records")."""
+    inp, keep = _alignment_input(seqs)
+    m = _alignment_matrix(matrix)
+    ns = inp.nseqs
+    scores = (C.c_int32 * max(ns * ns, 1))()
+    r = AlignmentResult(scores=C.addressof(scores))
+    npairs = alignment_bounds([list(keep[2][keep[1][i]:keep[1][i] + keep[0][i]]) for i in range(ns)], cutoff)["pairs"] \
+        if pairs else 0
+    recs = (AlignmentPair * max(npairs, 1))() if pairs else None
+    _check(lib().hclib_hip_alignment(C.byref(inp), C.byref(m), cutoff, C.byref(r), recs), "hclib_hip_alignment")
+    out = {k: getattr(r, k) for k, _ in AlignmentResult._fields_ if k != "scores"}
+    out["scores"] = [list(scores[i * ns:(i + 1) * ns]) for i in range(ns)]
+    if pairs:
+        out["pair_records"] = [{k: getattr(q, k) for k, _ in AlignmentPair._fields_} for q in recs[:npairs]]
+    return out
+
+
+def alignment_last_ticks() -> dict:
+    """Wave time of the last alignment() by task class, in ticks of the 100 MHz
+    device clock (hclib_hip_alignment_last_ticks): ALIGNMENT_TICKS."""
+    out = (C.c_uint64 * 4)()
+    lib().hclib_hip_alignment_last_ticks(out)
+    return dict(zip(ALIGNMENT_TICKS, out))
 
 
 ATOMIC_SCATTER_RET64 = 0  # include/hclib_hip.h

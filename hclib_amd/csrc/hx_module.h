@@ -32,6 +32,7 @@ enum ArenaId {
     kArenaSort,        // class counters, the array and tmp
     kArenaStrassen,    // class counters, A, B, C and the temporaries
     kArenaHealth,      // class counters, village tables, patient records and the lists' arena
+    kArenaAlignment,   // class counters, matrix, sequence and pair tables, pair records, codes, row slices
     kArenaUtsTables,   // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };

@@ -64,6 +64,13 @@
  *                                    floorplan.c:230-328), as a task kind of the
  *                                    work-stealing megakernel with the bound as one
  *                                    word every XCD reads and lowers
+ *   hclib_hip_alignment              the hclib_start_finish and its hclib_async per
+ *                                    sequence pair of BOTS alignment (bots/
+ *                                    alignment_for, alignment_single: alignment.c;
+ *                                    the algorithm alignment.ref.c:204-529), the two
+ *                                    halves of Myers-Miller's diff as further tasks,
+ *                                    every sweep a wave-wide task body, as one launch
+ *                                    of dynamic device dataflow
  *   hclib_hip_atomic_*,              the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -965,6 +972,101 @@ typedef struct {
 int hclib_hip_floorplan(const hclib_hip_floorplan_input_t *in, int flags, hclib_hip_floorplan_result_t *result,
                         uint8_t *board /* 4096, may be NULL */, uint64_t *hist /* n + 1, may be NULL */);
 int hclib_hip_floorplan_read_input(const char *path, hclib_hip_floorplan_input_t *out);
+
+/* ------------------------------------------------------------ Alignment */
+/* BOTS alignment (test/performance-regression/full-apps/bots/alignment_for and
+ * alignment_single: alignment.ref.c the algorithm, alignment.c the HClib port,
+ * one hclib_async per sequence pair inside one hclib_start_finish; the two
+ * programs differ only in the host loop that creates those tasks) as ONE
+ * launch of dynamic device dataflow: every pair si < sj of the input aligned
+ * by forward_pass, reverse_pass and Myers-Miller's diff with affine gaps, the
+ * protein branch, and scored by the percentage of identical residues on the
+ * alignment's diagonal steps. A task per pair runs the two passes and the root
+ * diff; a diff of more than `cutoff` cells (M * N) computes its midpoint and
+ * creates its two halves as tasks, a smaller one runs the whole recursion below
+ * it from a stack in LDS. Every task body is wave-wide and is the serial
+ * recurrence itself (hclib_amd/csrc/alignment.hip has the sweep). Integers
+ * only on the device; the gap-open penalty (a log) and the final percentage
+ * are computed on the host in double as the reference computes them, so every
+ * score and every field of a pair's record equals the reference's on any
+ * schedule and at any cutoff.
+ * input: nseqs sequences of residue codes 0..24 by "ABCDEFGHIKLMNPQRSTUVWXYZ-",
+ * a '-' of the file as 31; sequence i is codes[offset[i] .. offset[i] +
+ * length[i]). names (may be NULL) has 31 bytes per sequence.
+ * matrix: mat_avscore and matrix[32][32] as the reference's get_matrix leaves
+ * them; the library carries no substitution table of its own.
+ * cutoff: cells, at least 1; 0 chooses the default 16384.
+ * result: scores, the caller's nseqs x nseqs ints, receives bench_output (the
+ * upper triangle, zeros elsewhere, 1 for a pair with an empty sequence). pairs
+ * = the pairs without an empty sequence, each a pair task. tasks = what the
+ * device ran = 1 + pairs + 2 x (diffs that created their halves); created = the
+ * tasks device tasks created (tasks - 1); promises = 0. pair_tasks, spawn_tasks
+ * and leaf_tasks count the tasks by class: pairs, diff tasks that created their
+ * halves, diff tasks that did not. matches, diff_calls, type2 and ties are the
+ * sums of the records. cells = the sum of n * m over the pairs; cells_per_s =
+ * cells / kernel time; uploads and the download are outside kernel_ms.
+ * pairs (may be NULL; `pairs` entries, hclib_hip_alignment_bounds out[0]), in
+ * (si, sj) order: si, sj (from 0), g, gh, what the passes found (maxscore, se1,
+ * se2, sb1, sb2, positions from 1), and over the pair's diff tree: matches
+ * (diagonal steps with equal residues that are no gap codes), diff_calls (every
+ * invocation, base cases included), type2 (midpoints of type 2) and ties (takes
+ * of the midpoint scan's hh == midh && HH[j] != DD[j] && RR[j] == SS[j]
+ * branch).
+ * HCLIB_HIP_EINVAL before the device is touched: a NULL input, matrix, result
+ * or result->scores; nseqs < 1; a length below 0 or above 4999 (the
+ * reference's MAX_ALN_LENGTH arrays hold no more, and it would overflow them
+ * silently); a sequence outside codes; a code above 31; cutoff < 0; a matrix
+ * whose avscore makes a gap penalty negative.
+ * hclib_hip_alignment_read_input: host only, no GPU: a Pearson file with the
+ * reference's behaviour (readseqs, sequence.c:120-186): the `Number of
+ * sequences is <n>` line, names up to the first blank, only the 24 upper-case
+ * letters of the code string and '-' kept (the reference's table maps a
+ * lower-case letter to its upper-case one and then rejects it by comparison),
+ * an empty sequence legal when a line follows its header. EINVAL for a file the
+ * reference would read out of bounds on: no count line, fewer sequences than
+ * the count, a last header with nothing after it, a sequence over 4999. The
+ * arrays are the library's; give them back with _free_input.
+ * hclib_hip_alignment_read_matrix: host only: a matrix file, '#' comment lines,
+ * `avscore <int>`, then 32 x 32 integers.
+ * hclib_hip_alignment_bounds: host only: out[0] pairs (exact), and upper bounds
+ * in closed form on what a launch at this cutoff uses: out[1] tasks, out[2]
+ * diffs that create their halves, out[3] diff calls, out[4] bytes of the arena
+ * with the most resident waves a launch can have, out[5] bytes of one wave's
+ * row arrays in it (0: they are in LDS, the longest sequence has at most 767
+ * residues). The pools of a launch are sized from these. The same checks.
+ * hclib_hip_alignment_last_ticks: where the last launch's wave time went, ticks
+ * of the 100 MHz device clock summed over the tasks of each class: [0] the
+ * root, [1] pair tasks, [2] diff tasks that created their halves, [3] diff
+ * tasks that did not. */
+typedef struct {
+    int32_t nseqs, total; /* total: entries of codes */
+    int32_t *length;      /* nseqs */
+    int32_t *offset;      /* nseqs */
+    uint8_t *codes;       /* total */
+    char *names;          /* nseqs x 31, or NULL */
+} hclib_hip_alignment_input_t;
+typedef struct {
+    int32_t avscore;
+    int32_t score[32][32];
+} hclib_hip_alignment_matrix_t;
+typedef struct {
+    int32_t si, sj, g, gh, maxscore, se1, se2, sb1, sb2, matches, diff_calls, type2, ties;
+} hclib_hip_alignment_pair_t;
+typedef struct {
+    int32_t *scores; /* nseqs x nseqs, the caller's */
+    uint64_t pairs, tasks, created, promises, pair_tasks, spawn_tasks, leaf_tasks;
+    uint64_t matches, diff_calls, type2, ties, cells;
+    int32_t cutoff; /* the cutoff used */
+    double kernel_ms; /* device events around the one launch */
+    double cells_per_s;
+} hclib_hip_alignment_result_t;
+int hclib_hip_alignment(const hclib_hip_alignment_input_t *input, const hclib_hip_alignment_matrix_t *matrix, int cutoff,
+                        hclib_hip_alignment_result_t *result, hclib_hip_alignment_pair_t *pairs /* may be NULL */);
+int hclib_hip_alignment_read_input(const char *path, hclib_hip_alignment_input_t *out);
+void hclib_hip_alignment_free_input(hclib_hip_alignment_input_t *in);
+int hclib_hip_alignment_read_matrix(const char *path, hclib_hip_alignment_matrix_t *out);
+int hclib_hip_alignment_bounds(const hclib_hip_alignment_input_t *input, int cutoff, uint64_t out[6]);
+void hclib_hip_alignment_last_ticks(uint64_t out[4]);
 
 #ifdef __cplusplus
 }
