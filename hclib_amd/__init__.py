@@ -137,6 +137,15 @@ class StrassenResult(C.Structure):
                 ("kernel_ms", C.c_double), ("gflops", C.c_double)]
 
 
+class FftResult(C.Structure):
+    """hclib_hip_fft_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("leaves", C.c_uint64), ("calls", C.c_uint64), ("unsh_bands", C.c_uint64),
+                ("twid_bands", C.c_uint64), ("finishes", C.c_uint64), ("check_ins", C.c_uint64),
+                ("bytes_moved", C.c_uint64), ("nfactors", C.c_int32), ("factors", C.c_int32 * 40),
+                ("cutoff", C.c_int32), ("band", C.c_int32), ("kernel_ms", C.c_double), ("gbytes_per_s", C.c_double)]
+
+
 class HealthParams(C.Structure):
     """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
 
@@ -244,6 +253,7 @@ EXPORTS_HIP = [
     "hclib_hip_floorplan", "hclib_hip_floorplan_read_input",
     "hclib_hip_alignment", "hclib_hip_alignment_read_input", "hclib_hip_alignment_free_input",
     "hclib_hip_alignment_read_matrix", "hclib_hip_alignment_bounds", "hclib_hip_alignment_last_ticks",
+    "hclib_hip_fft", "hclib_hip_fft_factors", "hclib_hip_fft_twiddles", "hclib_hip_fft_bounds", "hclib_hip_fft_last_ticks",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -349,6 +359,12 @@ def lib():
         L.hclib_hip_alignment_bounds.argtypes = [C.POINTER(AlignmentInput), C.c_int, C.POINTER(C.c_uint64)]
         L.hclib_hip_alignment_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
         L.hclib_hip_alignment_last_ticks.restype = None
+        L.hclib_hip_fft.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(FftResult)]
+        L.hclib_hip_fft_factors.argtypes = [C.c_int, C.POINTER(C.c_int)]
+        L.hclib_hip_fft_twiddles.argtypes = [C.c_int, C.c_void_p]
+        L.hclib_hip_fft_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_fft_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
+        L.hclib_hip_fft_last_ticks.restype = None
         _lib = L
     return _lib
 
@@ -977,6 +993,78 @@ def strassen_last_ticks() -> dict:
     out = (C.c_uint64 * 6)()
     lib().hclib_hip_strassen_last_ticks(out)
     return dict(zip(("multiply", "pre", "combine", "split", "fork", "post"), out))
+
+
+# ------------------------------------------------------------------ BOTS fft
+def fft(x, w=None, cutoff: int = 0, band: int = 0):
+    """BOTS fft on dynamic device dataflow (hclib_hip_fft): x is a complex128
+    vector of n points; returns (fft_seq's output given the table w, bit for
+    bit, stats). w is the twiddle table the transform reads, n + 1 entries as a
+    complex128 vector or an (n + 1, 2) float64 array: the reference's own table
+    gives the reference's bits; None means fft_twiddles(n). cutoff is the
+    largest call that runs as one task (0 = 8192, at least 32), band the
+    columns per band task of the two sweeps (0 = 256, or 1024 for n above 2^22; a
+    multiple of 64);
+    results depend on neither."""
+    import numpy as np
+
+    x = np.ascontiguousarray(x, dtype=np.complex128)
+    if x.ndim != 1:
+        raise ValueError("fft: x must be a vector")
+    n = x.shape[0]
+    wp = None
+    if w is not None:
+        w = np.ascontiguousarray(w)
+        w = np.ascontiguousarray(w, dtype=np.complex128 if np.iscomplexobj(w) else np.float64)
+        if w.size * (2 if np.iscomplexobj(w) else 1) != 2 * (n + 1):
+            raise ValueError("fft: w must hold n + 1 (re, im) pairs")
+        wp = w.ctypes.data
+    out = np.empty_like(x)
+    r = FftResult()
+    _check(lib().hclib_hip_fft(x.ctypes.data, out.ctypes.data, n, wp, cutoff, band, C.byref(r)), "hclib_hip_fft")
+    st = {k: getattr(r, k) for k, _ in FftResult._fields_ if k not in ("factors", "nfactors")}
+    st["factors"] = list(r.factors[:r.nfactors])
+    return out, st
+
+
+def fft_factors(n: int) -> list:
+    """fft_seq's factor list of n (hclib_hip_fft_factors, host only)."""
+    out = (C.c_int * 40)()
+    cnt = lib().hclib_hip_fft_factors(n, out)
+    if cnt < 0:
+        _check(cnt, "hclib_hip_fft_factors")
+    return list(out[:cnt])
+
+
+def fft_twiddles(n: int):
+    """The table compute_w_coefficients fills, by the reference's formula and
+    write order through this host's cos and sin: (n + 1, 2) float64
+    (hclib_hip_fft_twiddles, host only). The reference's binary differs from it
+    in the last bit of a few entries, so its own table is an input of fft()."""
+    import numpy as np
+
+    if n < 1:
+        _check(lib().hclib_hip_fft_twiddles(n, None), "hclib_hip_fft_twiddles")
+    w = np.empty((n + 1, 2), dtype=np.float64)
+    _check(lib().hclib_hip_fft_twiddles(n, w.ctypes.data), "hclib_hip_fft_twiddles")
+    return w
+
+
+def fft_bounds(n: int, cutoff: int = 0, band: int = 0) -> dict:
+    """What an fft() of n points creates (hclib_hip_fft_bounds), exact and on the
+    host alone: device tasks, finish scopes, wait nodes, leaf tasks, band tasks
+    and the bytes its passes move."""
+    out = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_fft_bounds(n, cutoff, band, out), "hclib_hip_fft_bounds")
+    return dict(zip(("tasks", "scopes", "nodes", "leaves", "bands", "bytes"), out))
+
+
+def fft_last_ticks() -> dict:
+    """Wave time of the last fft() by task class, in ticks of the 100 MHz device
+    clock (hclib_hip_fft_last_ticks)."""
+    out = (C.c_uint64 * 6)()
+    lib().hclib_hip_fft_last_ticks(out)
+    return dict(zip(("leaf", "unsh", "twid", "call", "fork", "post"), out))
 
 
 # --------------------------------------------------------------- BOTS Health

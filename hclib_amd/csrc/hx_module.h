@@ -33,7 +33,8 @@ enum ArenaId {
     kArenaStrassen,    // class counters, A, B, C and the temporaries
     kArenaHealth,      // class counters, village tables, patient records and the lists' arena
     kArenaAlignment,   // class counters, matrix, sequence and pair tables, pair records, codes, row slices
-    kArenaUtsTables,   // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
+    kArenaFft,         // class counters, the two ping-pong buffers and the twiddle table
+    kArenaUtsTables,  // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };
 struct Arena {

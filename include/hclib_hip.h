@@ -71,7 +71,13 @@
  *                                    halves of Myers-Miller's diff as further tasks,
  *                                    every sweep a wave-wide task body, as one launch
  *                                    of dynamic device dataflow
- *   hclib_hip_atomic_*,              the per-thread copies and the gather of
+ *   hclib_hip_fft                    the three taskwaits of BOTS fft's fft_aux
+ *                                    (bots/fft/fft.c, fft.ref.c:4653-4747) as finish
+ *                                    scopes and continuations, the unshuffle and
+ *                                    twiddle sweeps as band tasks, the r asyncs as
+ *                                    child tasks, as one launch of dynamic device
+ *                                    dataflow
+ *   hclib_hip_atomic_*,            the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
  *
@@ -1067,6 +1073,53 @@ void hclib_hip_alignment_free_input(hclib_hip_alignment_input_t *in);
 int hclib_hip_alignment_read_matrix(const char *path, hclib_hip_alignment_matrix_t *out);
 int hclib_hip_alignment_bounds(const hclib_hip_alignment_input_t *input, int cutoff, uint64_t out[6]);
 void hclib_hip_alignment_last_ticks(uint64_t out[4]);
+
+/* BOTS fft (test/performance-regression/full-apps/bots/fft: fft.ref.c the
+ * algorithm, fft.c the HClib port): the Cilk mixed-radix transform fft_seq(n,
+ * in, out) as ONE launch of dynamic device dataflow, every output bit-identical
+ * to the reference's given the reference's twiddle table. A call above the
+ * cutoff is a task that opens a finish scope for the bands of its unshuffle, a
+ * continuation that opens one for its r children (the two buffers' roles
+ * swapped), and a continuation that runs the twiddle sweep as bands
+ * (hclib_amd/csrc/fft.hip has the task table); a call of at most `cutoff`
+ * points, and every base of 2 .. 32 points, is one task that runs its whole
+ * subtree pass by pass. Radix-2 / 4 / 8 / 16 columns are butterflies in a
+ * lane's registers, f64 VALU without fused multiply-add.
+ * `in` and `out` are n interleaved (re, im) pairs of the host; `in` is not
+ * written. `w` is the table W of n + 1 (re, im) pairs the transform reads, an
+ * input: the reference's binary computes it with a libm call whose last bit no
+ * formula restates, so a caller that wants the reference's bits passes the
+ * reference's table. NULL: hclib_hip_fft_twiddles(n), the reference's formula
+ * and write order through this host's cos and sin.
+ * cutoff: 0 (8192) or at least 32. band: columns (for the general radix,
+ * outputs) per band task, 0 (256, or 1024 for n above 2^22) or a multiple of
+ * 64. Results depend on neither. The launch reads HCLIB_HIP_FFT_WAVES_PER_CU
+ * (1, or 4 for n above 2^22; at most 8). EINVAL unless 1 <= n <= 2^26 and n's largest prime factor is at most
+ * 512; ENOMEM where the device cannot hold 3 x 16 n bytes.
+ * hclib_hip_fft_factors: host only: fft_seq's factor list, its length returned
+ * (negative: EINVAL). Calls of 2 .. 32 points are bases whatever the list says.
+ * hclib_hip_fft_twiddles: host only: n + 1 pairs into w.
+ * hclib_hip_fft_bounds: host only, exact: out[0] tasks, out[1] finish scopes,
+ * out[2] wait nodes, out[3] leaf tasks, out[4] band tasks, out[5] bytes the
+ * passes move (32 n per pass: every pass reads and writes each pair once).
+ * hclib_hip_fft_last_ticks: where the last launch's wave time went, ticks of
+ * the 100 MHz device clock summed over the tasks of each class: [0] leaves,
+ * [1] UNSH bands, [2] TWID bands, [3] CALL, [4] FORK, [5] POST. */
+typedef struct {
+    uint64_t tasks, leaves, calls, unsh_bands, twid_bands;
+    uint64_t finishes, check_ins;
+    uint64_t bytes_moved;      /* out[5] of _bounds */
+    int32_t nfactors, factors[40];
+    int32_t cutoff, band;      /* the values used */
+    double kernel_ms;          /* device events around the one launch */
+    double gbytes_per_s;       /* bytes_moved / kernel_ms */
+} hclib_hip_fft_result_t;
+int hclib_hip_fft(const double *in, double *out, int n, const double *w /* n + 1 pairs, or NULL */, int cutoff, int band,
+                  hclib_hip_fft_result_t *result);
+int hclib_hip_fft_factors(int n, int out[40]);
+int hclib_hip_fft_twiddles(int n, double *w);
+int hclib_hip_fft_bounds(int n, int cutoff, int band, uint64_t out[6]);
+void hclib_hip_fft_last_ticks(uint64_t out[6]);
 
 #ifdef __cplusplus
 }
