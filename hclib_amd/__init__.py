@@ -146,6 +146,14 @@ class FftResult(C.Structure):
                 ("cutoff", C.c_int32), ("band", C.c_int32), ("kernel_ms", C.c_double), ("gbytes_per_s", C.c_double)]
 
 
+class JacobiResult(C.Structure):
+    """hclib_hip_jacobi_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("puts", C.c_uint64), ("releases", C.c_uint64), ("supersteps", C.c_uint64),
+                ("bytes_moved", C.c_uint64), ("block", C.c_int), ("fuse", C.c_int), ("wgs_per_cu", C.c_int),
+                ("kernel_ms", C.c_double), ("gbytes_per_s", C.c_double), ("gcells_per_s", C.c_double)]
+
+
 class HealthParams(C.Structure):
     """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
 
@@ -254,6 +262,7 @@ EXPORTS_HIP = [
     "hclib_hip_alignment", "hclib_hip_alignment_read_input", "hclib_hip_alignment_free_input",
     "hclib_hip_alignment_read_matrix", "hclib_hip_alignment_bounds", "hclib_hip_alignment_last_ticks",
     "hclib_hip_fft", "hclib_hip_fft_factors", "hclib_hip_fft_twiddles", "hclib_hip_fft_bounds", "hclib_hip_fft_last_ticks",
+    "hclib_hip_jacobi", "hclib_hip_jacobi_rhs", "hclib_hip_jacobi_bounds",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -365,6 +374,10 @@ def lib():
         L.hclib_hip_fft_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.hclib_hip_fft_last_ticks.argtypes = [C.POINTER(C.c_uint64)]
         L.hclib_hip_fft_last_ticks.restype = None
+        L.hclib_hip_jacobi.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, C.c_double, C.c_int, C.c_int,
+                                       C.c_int, C.c_void_p, C.POINTER(JacobiResult)]
+        L.hclib_hip_jacobi_rhs.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.hclib_hip_jacobi_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -1065,6 +1078,52 @@ def fft_last_ticks() -> dict:
     out = (C.c_uint64 * 6)()
     lib().hclib_hip_fft_last_ticks(out)
     return dict(zip(("leaf", "unsh", "twid", "call", "fork", "post"), out))
+
+
+# ------------------------------------------------------------ Kastors Jacobi
+def jacobi(f, unew0, dx=None, dy=None, block: int = 0, niter: int = 4, fuse: int = 0):
+    """Kastors jacobi on the device promise DAG (hclib_hip_jacobi): niter sweeps of
+    the 5-point stencil over the (nx, ny) float64 grid unew0 with right-hand side
+    and boundary values f; returns (sweep_seq's unew, bit for bit, stats). dx and
+    dy default to run()'s 1 / (nx - 1) and 1 / (ny - 1). block (0 = 128, the
+    reference's default, which is above what fits: name one with block + 2 fuse
+    <= 82) must divide both sides; a task advances its block by up to fuse
+    sweeps (0 = the default) from LDS; results depend on neither."""
+    import numpy as np
+
+    f = np.ascontiguousarray(f, dtype=np.float64)
+    unew0 = np.ascontiguousarray(unew0, dtype=np.float64)
+    if f.ndim != 2 or f.shape != unew0.shape:
+        raise ValueError("jacobi: f and unew0 must be matrices of one shape")
+    nx, ny = f.shape
+    dx = 1.0 / (nx - 1) if dx is None else dx
+    dy = 1.0 / (ny - 1) if dy is None else dy
+    out = np.empty_like(unew0)
+    r = JacobiResult()
+    _check(lib().hclib_hip_jacobi(f.ctypes.data, unew0.ctypes.data, nx, ny, dx, dy, block, niter, fuse, out.ctypes.data,
+                                  C.byref(r)), "hclib_hip_jacobi")
+    return out, {k: getattr(r, k) for k, _ in JacobiResult._fields_}
+
+
+def jacobi_rhs(nx: int, ny: int):
+    """(f, unew0) of the reference's rhs() and run() for an (nx, ny) grid, through
+    this host's libm (hclib_hip_jacobi_rhs, host only)."""
+    import numpy as np
+
+    if nx < 3 or ny < 3:
+        _check(lib().hclib_hip_jacobi_rhs(nx, ny, None, None), "hclib_hip_jacobi_rhs")
+    f, u = np.empty((nx, ny), dtype=np.float64), np.empty((nx, ny), dtype=np.float64)
+    _check(lib().hclib_hip_jacobi_rhs(nx, ny, f.ctypes.data, u.ctypes.data), "hclib_hip_jacobi_rhs")
+    return f, u
+
+
+def jacobi_bounds(nx: int, ny: int, block: int = 0, niter: int = 4, fuse: int = 0) -> dict:
+    """What a jacobi() launch creates (hclib_hip_jacobi_bounds), exact and on the
+    host alone: tasks, awaits, supersteps and the bytes the tasks move. Raises as
+    the launch would for arguments it rejects."""
+    out = (C.c_uint64 * 4)()
+    _check(lib().hclib_hip_jacobi_bounds(nx, ny, block, niter, fuse, out), "hclib_hip_jacobi_bounds")
+    return dict(zip(("tasks", "awaits", "supersteps", "bytes_moved"), out))
 
 
 # --------------------------------------------------------------- BOTS Health

@@ -34,6 +34,7 @@ enum ArenaId {
     kArenaHealth,      // class counters, village tables, patient records and the lists' arena
     kArenaAlignment,   // class counters, matrix, sequence and pair tables, pair records, codes, row slices
     kArenaFft,         // class counters, the two ping-pong buffers and the twiddle table
+    kArenaJacobi,      // f and the two ping-pong grids
     kArenaUtsTables,  // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };

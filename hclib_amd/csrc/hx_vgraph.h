@@ -31,11 +31,17 @@ struct VersionGraph {
     }
     uint32_t ntasks() const { return (uint32_t)(off.size() - 1); }
     void task(uint32_t kind, uint32_t a, uint32_t b, uint32_t c, size_t writes, std::initializer_list<size_t> reads) {
+        task(kind, a, b, c, writes, reads.begin(), reads.size());
+    }
+    // the same for a read set whose size is known only at run time (hx_jacobi_plan.h)
+    void task(uint32_t kind, uint32_t a, uint32_t b, uint32_t c, size_t writes, const size_t *reads, size_t nreads) {
         const uint32_t id = ntasks();
         const uint32_t pl[4] = {kind, a, b, c};
         payload.insert(payload.end(), pl, pl + 4);
-        for (size_t r : reads)
+        for (size_t k = 0; k < nreads; ++k) {
+            const size_t r = reads[k];
             if (last_[r] != kNone) ids.push_back(last_[r]);
+        }
         off.push_back((uint32_t)ids.size());
         last_[writes] = id;
     }

@@ -77,6 +77,12 @@
  *                                    twiddle sweeps as band tasks, the r asyncs as
  *                                    child tasks, as one launch of dynamic device
  *                                    dataflow
+ *   hclib_hip_jacobi                 the copy and compute phases of Kastors jacobi's
+ *                                    sweep() and the hclib_end_finish after each
+ *                                    (kastors-1.1/jacobi/src/jacobi-block-task.c:
+ *                                    57-108), as neighbour awaits between block
+ *                                    tasks of consecutive (time-fused) sweeps in
+ *                                    one launch of the device promise DAG
  *   hclib_hip_atomic_*,            the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -1120,6 +1126,48 @@ int hclib_hip_fft_factors(int n, int out[40]);
 int hclib_hip_fft_twiddles(int n, double *w);
 int hclib_hip_fft_bounds(int n, int cutoff, int band, uint64_t out[6]);
 void hclib_hip_fft_last_ticks(uint64_t out[6]);
+
+/* Kastors Jacobi (test/performance-regression/full-apps/kastors-1.1/jacobi:
+ * jacobi-seq.c the rule, jacobi-task.c, jacobi-block-task.c and
+ * jacobi-block-for.c its three parallel sweeps, poisson.c the driver): niter
+ * sweeps of the 5-point stencil over a row-major nx x ny grid of doubles,
+ * a[i * ny + j], as ONE launch of the device promise DAG with no barrier
+ * between sweeps. Per sweep a boundary cell becomes f, every other cell
+ * 0.25 * ((((u[i-1][j] + u[i][j+1]) + u[i][j-1]) + u[i+1][j]) + (f[i][j] * dx) * dy)
+ * of the sweep before, every operation rounded on its own: the bits of
+ * sweep_seq and of the three parallel forms.
+ * A task advances one block x block tile by up to `fuse` sweeps from LDS: it
+ * reads a halo `fuse` cells wide and recomputes the overlap, which divides the
+ * memory traffic and the task count by nearly `fuse` and changes no bit
+ * (hclib_amd/csrc/hx_jacobi_plan.h has the graph, jacobi.hip the body).
+ * f, unew0 (the initial estimate, poisson.c's unew before sweep()) and unew are
+ * host arrays of nx * ny doubles; f and unew0 are not written. niter = 0
+ * launches nothing and copies unew0.
+ * block: 0 = 128 (run()'s default), else it must divide nx and ny. fuse: 0 =
+ * the default (4, or what the block allows), else 1 <= fuse <= block. EINVAL,
+ * before the device is touched, unless nx, ny >= 3, niter >= 0, the block
+ * divides both sides, block + 2 * fuse <= 82 (three images of a task's region
+ * in the CU's LDS; the reference's default block of 128 does not fit, so a
+ * caller names a smaller one) and the launch has fewer than 2^26 tasks. Results depend on neither block
+ * nor fuse. The launch reads HCLIB_HIP_JACOBI_WGS_PER_CU (default and at most:
+ * what the region's LDS allows, 1, 2 or 4).
+ * hclib_hip_jacobi_rhs: host only: rhs() and run()'s initial estimate through
+ * the host's libm (either array may be NULL).
+ * hclib_hip_jacobi_bounds: host only, exact: out[0] tasks, out[1] awaits,
+ * out[2] supersteps, out[3] bytes moved (per task the clipped region of u it
+ * reads, the cells of f its sweeps read and the block it writes, times 8);
+ * EINVAL as the launch would. */
+typedef struct {
+    uint64_t tasks, puts, releases;      /* from the DAG launch */
+    uint64_t supersteps, bytes_moved;    /* the plan's */
+    int block, fuse, wgs_per_cu;         /* as run */
+    double kernel_ms;                    /* device events around the one launch */
+    double gbytes_per_s, gcells_per_s;   /* bytes_moved, and nx*ny*niter, over kernel time */
+} hclib_hip_jacobi_result_t;
+int hclib_hip_jacobi(const double *f, const double *unew0, int nx, int ny, double dx, double dy,
+                     int block, int niter, int fuse, double *unew, hclib_hip_jacobi_result_t *result);
+int hclib_hip_jacobi_rhs(int nx, int ny, double *f, double *unew0);
+int hclib_hip_jacobi_bounds(int nx, int ny, int block, int niter, int fuse, uint64_t out[4]);
 
 #ifdef __cplusplus
 }
