@@ -650,10 +650,12 @@ __device__ void run_dag_group(const typename Kind::Ctx &ctx, const DagView &view
                         w.puts += N;
                         w.releases += rel;
                     } else {
-                        // long waiter lists: the ordinary batched put (it appends
-                        // its releases itself)
+                        // long waiter lists: the ordinary batched put. Its total
+                        // is nwait (the same promises), so it takes its
+                        // promise-by-promise fallback, which appends every
+                        // release itself and keeps no task: wave 0 goes on to
+                        // a ticket (tests/hip/device_dag_forms.hip)
                         dag_put_n<N, Kind::kSc1Payload>(w, p, d);
-                        if (w.next != kDagEmpty && lane == w.skip_lane) st_agent(&view.ready[w.skip_pos], kDagSkip);
                     }
                     if (lane == 0) {
                         sh.npend = 0;

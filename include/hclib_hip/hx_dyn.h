@@ -306,6 +306,14 @@ __device__ void run_dyn_worker(const typename Kind::Ctx &ctx, const DynView &vie
     DynWave w{view, 0, 0, 0, 0, 0};
     const int lane = lane_id();
     while (true) {
+        // every lane starts an iteration here, together. Without this point
+        // the compiler may fuse the lane-0 decrement that ends an iteration
+        // with the lane-0 ticket fetch of the next one and split the loop in
+        // two around them; lanes 1..63 then reach the readfirstlane below
+        // without lane 0, read an empty ticket and leave, and lane 0 runs
+        // every later task of the wave alone (tests/hip/device_dyn_limits.hip
+        // counts bodies entered by fewer than 64 lanes)
+        __builtin_amdgcn_wave_barrier();
         uint32_t ticket = 0;
         if (lane == 0) ticket = add_agent(dyn_head(view), 1u);
         ticket = (uint32_t)__builtin_amdgcn_readfirstlane((int)ticket);

@@ -116,3 +116,23 @@ def test_non_spd_matrix_returns_the_reference_error(tile):
     l, st = H.cholesky(_input(50), 10)
     assert np.array_equal(l, _ref(50))
     _counts(st, 5)
+
+
+def test_seventy_tiles_per_side_take_the_long_waiter_list_put():
+    """nt = 70 (59,640 tasks): potrf(0)'s promise has 69 waiters (the trsm of
+    column 0), trsm(i, 0)'s likewise, so these puts take the more-than-64-waiters
+    branch of run_dag_group's plain split put (include/hclib_hip/hx_dag.h: the
+    helper wave prefetches and publishes nothing, wave 0 puts through
+    dag_put_n's promise-by-promise fallback). The other GPU cases stop at
+    nt = 25 and never enter it."""
+    a = R.spd_matrix(140, 7)
+    l, st = H.cholesky(a, 2)
+    want = R.reference("spd140", lambda: a, 2)
+    assert np.isfinite(want).all()
+    assert np.array_equal(l, want)
+    _upper_is_plus_zero(l)
+    _counts(st, 70)
+    assert st["tasks"] == 59640
+    l20, st20 = H.cholesky(a, 20)
+    _counts(st20, 7)
+    assert np.array_equal(l, l20)

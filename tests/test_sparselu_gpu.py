@@ -98,3 +98,19 @@ def test_c_program_prints_the_structure_and_a_checksum(tmp_path):
     assert "Structure for matrix benchmark\n" + H.sparselu_structure(want_mask) in r.stdout
     assert "80 tasks (7 lu0, 15 fwd, 15 bdiv, 43 bmod), 25 -> 37 blocks" in r.stdout
     assert "checksum %d\n" % int(want.view(np.uint32).astype(np.uint64).sum()) in r.stdout
+
+
+def test_dense_36_blocks_per_side_take_the_long_waiter_list_put():
+    """S = 36, dense: lu0(0)'s promise has 2 (S - 1) = 70 waiters (the fwd and
+    bdiv tasks of step 0), more than the 64 that run_dag_group's plain split
+    put prefetches (include/hclib_hip/hx_dag.h), so it goes through dag_put_n's
+    promise-by-promise fallback. The other GPU cases stop at S = 16. The plan
+    is asked first, so that a change of plan cannot empty this test silently."""
+    S, B = 36, 2
+    mask, _ = R.dense_input(S, B, 36002)
+    p = H.sparselu_plan(mask, graph=True)
+    waiters = np.bincount(p["await_ids"], minlength=p["tasks"])
+    assert waiters.max() > 64 and waiters[0] == 2 * (S - 1)
+    _, _, st = _check(("dense", S, B), lambda: R.dense_input(S, B, 36002), B)
+    assert st["blocks_in"] == st["blocks_out"] == S * S
+    assert st["bmod"] == (S - 1) * S * (2 * S - 1) // 6
