@@ -14,7 +14,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "hx_module.h"
+#include "hx_client.h"
 #include "../../include/hclib_hip/hx_finish.h"
 
 namespace hx {
@@ -270,8 +270,7 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
     }
     // 3 waves per CU with seeding (fib(30) 0.65 -> 0.48-0.49 ms against 2,
     // profiles/r04/fibseed2_sweep.log)
-    const int grid = env_int("HCLIB_HIP_GRID", 0) > 0 ? env_int("HCLIB_HIP_GRID", 0)
-                                                    : m.num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", 3);
+    const int grid = sched_grid(3);
     const int blocks = env_int("HCLIB_HIP_FIB_BLOCKS", 1);
     // the arena: every scope once, plus each wave's last partly used id block,
     // plus the seeding's reservation (worker 0 takes up to kFibSeedCap ids in
@@ -309,35 +308,28 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
         HX_HIP(hipMemsetAsync(ctx.seed, 0, 256, m.stream));
     }
     PoolView pool;
-    HX_TRY(make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64),
-                     (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
-                     // 32-item chunks at 2 waves per CU: fib(30) 1.47 -> 0.92 ms
-                     // (profiles/r02/fib_knobs.log; 8-item chunks made the 2,048
-                     // idle-polling waves of the old default fight over crumbs)
-                     (uint32_t)env_int("HCLIB_HIP_FIB_CHUNK", 32), FibKind::kWords, &pool));
-    SchedConfig cfg;
-    // seeded launches: 320 / 64 (fib(30) 0.49 -> 0.45 ms against 256 / 32,
-    // profiles/r04/fibknobs_f.log, fibknobs_g.log)
-    cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_FIB_SPILL_HI", seed_pw > 0 ? 320 : 256);
-    // scripts/sweep_uts.py fib30 (profiles/r01_s5/knob_sweeps.log): 32 -> 1.50 ms, 2 -> 1.70 ms
-    cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_FIB_SPILL_LO", seed_pw > 0 ? 64 : 32);
+    // 32-item chunks at 2 waves per CU: fib(30) 1.47 -> 0.92 ms
+    // (profiles/r02/fib_knobs.log; 8-item chunks made the 2,048
+    // idle-polling waves of the old default fight over crumbs)
+    HX_TRY(sched_pool(64, (uint32_t)env_int("HCLIB_HIP_FIB_CHUNK", 32), FibKind::kWords, &pool));
+    SchedConfig cfg = sched_config_unseeded("FIB", grid);
+    if (seed_pw > 0) {
+        // seeded launches: 320 / 64 (fib(30) 0.49 -> 0.45 ms against 256 / 32,
+        // profiles/r04/fibknobs_f.log, fibknobs_g.log)
+        cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_FIB_SPILL_HI", 320);
+        cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_FIB_SPILL_LO", 64);
+    }
     // seeded fib: its first batches see every wave busy, as the host set it
     // (fib(30) 0.40 -> 0.39 ms, profiles/r06/ab_outstpf.log)
     cfg.hunger_init_full = 1;
-    cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-    cfg.nwaves = (uint32_t)grid;
     cfg.stamps = (uint32_t)env_int("HCLIB_HIP_STAMPS", 0);
-    cfg.hunger = (uint32_t)env_int("HCLIB_HIP_FIB_HUNGER", 8);
-    cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
     // seeded: every wave starts holding its share (outstanding = every wave)
     HX_TRY(reset_sched(pool, ctx.seed ? (uint32_t)grid : 1u, false, (uint32_t)grid));
-    HX_HIP(hipEventRecord(m.ev0, m.stream));
-    HX_TRY(check_resident((const void *)k_fib, grid, 64, 0, "hclib_hip_fib"));
-    hipLaunchKernelGGL(k_fib, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
-    HX_HIP(hipGetLastError());
-    HX_HIP(hipEventRecord(m.ev1, m.stream));
     SchedGlobals gl;
-    int rc = finish_sched(&gl, "hclib_hip_fib");
+    float ms = 0;
+    int rc = launch_sched((const void *)k_fib, grid, 64, "hclib_hip_fib", [&] {
+        hipLaunchKernelGGL(k_fib, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
+    }, &gl, &ms);
     unsigned long long v = 0;
     if (rc == HCLIB_HIP_OK) rc = hip_check(hipMemcpy(&v, ctx.fin.root_value, 8, hipMemcpyDeviceToHost), "hipMemcpy");
     if (rc == HCLIB_HIP_OK && env_int("HCLIB_HIP_FIB_DEBUG", 0)) {
@@ -345,8 +337,6 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
         if (hipMemcpy(&used, ctx.fin.next, 4, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "fib(%d): %u of %llu scopes in HBM (local %d)\n", n, used, scopes - 1, ctx.local);
     }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
     if (rc != HCLIB_HIP_OK) return rc;
     *value = (int64_t)v;
     if (result) {
@@ -355,9 +345,7 @@ extern "C" int hclib_hip_fib(int n, int64_t *value, hclib_hip_fib_result_t *resu
         result->chunks_pushed = gl.counters[kCtrPushed];
         result->chunks_stolen = gl.counters[kCtrStolen];
         result->kernel_ms = ms;
-        const double busy = (double)gl.counters[kCtrBusyCycles],
-                     idle = (double)gl.counters[kCtrIdleCycles];
-        result->busy_frac = (busy + idle) > 0 ? busy / (busy + idle) : 0.0;
+        result->busy_frac = busy_frac(gl);
     }
     return HCLIB_HIP_OK;
 }

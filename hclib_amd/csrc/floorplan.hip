@@ -31,7 +31,7 @@
 
 #include <vector>
 
-#include "hx_module.h"
+#include "hx_client.h"
 
 namespace hx {
 
@@ -440,14 +440,6 @@ void fp_decode(const FpPlan &pl, int n, const uint32_t *t, hclib_hip_floorplan_r
     res->footprint[1] = fc;
 }
 
-template <class K>
-int fp_launch(const FpCtx &ctx, const PoolView &pool, const SchedConfig &cfg, int grid) {
-    Module &m = mod();
-    HX_TRY(check_resident((const void *)k_floorplan<K>, grid, 64, 0, "hclib_hip_floorplan"));
-    hipLaunchKernelGGL(k_floorplan<K>, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
-    return hip_check(hipGetLastError(), "hipLaunchKernelGGL(k_floorplan)");
-}
-
 }  // namespace
 
 extern "C" int hclib_hip_floorplan_read_input(const char *path, hclib_hip_floorplan_input_t *out) {
@@ -520,8 +512,7 @@ extern "C" int hclib_hip_floorplan(const hclib_hip_floorplan_input_t *in, int fl
     const int n = in->n;
     HX_TRY(ensure_device());
     Module &m = mod();
-    const int grid = env_int("HCLIB_HIP_GRID", 0) > 0 ? env_int("HCLIB_HIP_GRID", 0)
-                                                    : m.num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", 3);
+    const int grid = sched_grid(3);
     // one upload: the bound's line, the table, the histogram, the workers' records
     constexpr size_t kTabOff = 256, kTabBytes = (sizeof(uint32_t) * kFpTabWords + 255) & ~(size_t)255;
     constexpr size_t kHistOff = kTabOff + kTabBytes, kBestOff = kHistOff + 256;
@@ -542,28 +533,18 @@ extern "C" int hclib_hip_floorplan(const hclib_hip_floorplan_input_t *in, int fl
     ctx.hist = hist ? (unsigned long long *)(buf.p + kHistOff) : nullptr;
     ctx.best = (uint32_t *)(buf.p + kBestOff);
     PoolView pool;
-    SchedConfig cfg;
-    HX_TRY(make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
-                     (uint32_t)env_int("HCLIB_HIP_FLOORPLAN_CHUNK", 32), 8, &pool));
-    // the unseeded settings of fib and N-Queens: a batch pushes at most
-    // 64 * 10 range items, so 256 leaves the 1,024-item ring its room
-    cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_FLOORPLAN_SPILL_HI", 256);
-    cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_FLOORPLAN_SPILL_LO", 32);
-    cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-    cfg.nwaves = (uint32_t)grid;
-    cfg.stamps = 0;
-    cfg.hunger = (uint32_t)env_int("HCLIB_HIP_FLOORPLAN_HUNGER", 8);
-    cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
+    HX_TRY(sched_pool(64, (uint32_t)env_int("HCLIB_HIP_FLOORPLAN_CHUNK", 32), 8, &pool));
+    const SchedConfig cfg = sched_config_unseeded("FLOORPLAN", grid);
     HX_TRY(reset_sched(pool, 1u, false, (uint32_t)grid));
-    HX_HIP(hipEventRecord(m.ev0, m.stream));
-    HX_TRY(hist ? fp_launch<FpKind<true>>(ctx, pool, cfg, grid) : fp_launch<FpKind<false>>(ctx, pool, cfg, grid));
-    HX_HIP(hipEventRecord(m.ev1, m.stream));
+    void (*const kern)(FpCtx, PoolView, SchedGlobals *, SchedConfig) =
+        hist ? k_floorplan<FpKind<true>> : k_floorplan<FpKind<false>>;
     SchedGlobals gl;
-    HX_TRY(finish_sched(&gl, who));
+    float ms = 0;
+    HX_TRY(launch_sched((const void *)kern, grid, 64, who, [&] {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
+    }, &gl, &ms, "hipLaunchKernelGGL(k_floorplan)"));
     std::vector<uint32_t> back(bytes / 4);
     HX_HIP(hipMemcpy(back.data(), buf.p, bytes, hipMemcpyDeviceToHost));
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
     // the minimum over the workers' records; on equal area any of them is right
     // (the reference's winner under its critical section depends on the schedule too)
     const uint32_t *best = nullptr;
@@ -592,8 +573,7 @@ extern "C" int hclib_hip_floorplan(const hclib_hip_floorplan_input_t *in, int fl
     result->chunks_pushed = gl.counters[kCtrPushed];
     result->chunks_stolen = gl.counters[kCtrStolen];
     result->kernel_ms = ms;
-    const double busy = (double)gl.counters[kCtrBusyCycles], idle = (double)gl.counters[kCtrIdleCycles];
-    result->busy_frac = (busy + idle) > 0 ? busy / (busy + idle) : 0.0;
+    result->busy_frac = busy_frac(gl);
     if (hist)
         for (int i = 0; i <= n; ++i) hist[i] = ((const unsigned long long *)&back[kHistOff / 4])[i];
     return HCLIB_HIP_OK;

@@ -2,10 +2,13 @@
 // run_dag_group clients (cholesky.hip, sparselu.hip) the version graph, the
 // one-promise Kind and the launch; run_dyn_worker clients (sort.hip,
 // strassen.hip, health.hip) the per-class counters, the timed Kind and the
-// launch.
+// launch; run_worker clients (fib.hip, nqueens.hip, floorplan.hip, uts.hip) the
+// grid and pool knobs, the unseeded SchedConfig, the launch and busy_frac.
 #pragma once
 
 #include <string.h>
+
+#include <string>
 
 #include "hx_module.h"
 #include "hx_vgraph.h"
@@ -110,6 +113,82 @@ int launch_dyn(uint32_t words, const uint32_t *root, uint64_t tasks, uint64_t pr
     if (hipMemcpy(h, dev_counts, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess) memset(h, 0, sizeof(h));
     for (int k = 0; k < KINDS; ++k) cnt.tasks[k] = h[k * 32], cnt.ticks[k] = h[k * 32 + 1];
     return rc;
+}
+
+// ---------------------------------------------------------- run_worker clients
+// workers of a launch: HCLIB_HIP_GRID, else HCLIB_HIP_WAVES_PER_CU on every CU
+inline int sched_grid(int default_waves_per_cu) {
+    const int grid = env_int("HCLIB_HIP_GRID", 0);
+    return grid > 0 ? grid : mod().num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", default_waves_per_cu);
+}
+
+// the chunk deques: HCLIB_HIP_DEQUES (the client's default count) of
+// HCLIB_HIP_DEQUE_CAP slots, `chunk` items of `words` u32 per slot
+inline int sched_pool(int nq_default, uint32_t chunk, uint32_t words, PoolView *pool) {
+    return make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", nq_default), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
+                     chunk, words, pool);
+}
+
+// The settings of a launch that starts from one root, under the client's knob
+// names HCLIB_HIP_<CLIENT>_SPILL_HI / _SPILL_LO / _HUNGER: a batch pushes at
+// most 64 * 10 range items, so 256 leaves a 1,024-item ring its room; 32 / 8
+// from scripts/sweep_uts.py fib30 (profiles/r01_s5/knob_sweeps.log: spill_lo
+// 32 -> 1.50 ms, 2 -> 1.70 ms)
+inline SchedConfig sched_config_unseeded(const char *client, int grid) {
+    auto knob = [&](const char *name, int dflt) {
+        return (uint32_t)env_int((std::string("HCLIB_HIP_") + client + name).c_str(), dflt);
+    };
+    SchedConfig cfg;
+    cfg.spill_hi = knob("_SPILL_HI", 256);
+    cfg.spill_lo = knob("_SPILL_LO", 32);
+    cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
+    cfg.nwaves = (uint32_t)grid;
+    cfg.stamps = 0;
+    cfg.hunger = knob("_HUNGER", 8);
+    cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
+    return cfg;
+}
+
+// The end of a run_worker launch: the launch's own error (reported as
+// `launch_what` failing), the closing event, the globals and exit records
+// read back with the stream drained (finish_sched, which translates the
+// device error word), the time between the module's two events.
+inline int end_sched(const char *who, SchedGlobals *gl, float *kernel_ms, const char *launch_what = "hipGetLastError()") {
+    Module &m = mod();
+    HX_TRY(hip_check(hipGetLastError(), launch_what));
+    HX_HIP(hipEventRecord(m.ev1, m.stream));
+    const int rc = finish_sched(gl, who);
+    *kernel_ms = 0;
+    (void)hipEventElapsedTime(kernel_ms, m.ev0, m.ev1);
+    return rc;
+}
+
+// Runs a run_worker kernel `kern` (`blocks` workgroups of `threads`, no
+// dynamic LDS): `launch()` launches it on the module stream. The order
+// carries three conditions:
+//  1. reset_sched is the caller's (outstanding count and seeding differ) and
+//     is queued before this: the opening event follows it, so kernel_ms
+//     covers the pool reset as it always has.
+//  2. The workers wait for each other's work until the launch's outstanding
+//     count is zero, so the kernel is launched only if check_resident finds
+//     every workgroup resident; a refusal returns with nothing launched.
+//  3. A launched kernel is followed by finish_sched, which drains the
+//     stream: *gl is complete (also after a device error, whose code is
+//     returned) and the caller may read its results back with plain copies.
+template <class Launch>
+int launch_sched(const void *kern, int blocks, int threads, const char *who, Launch launch, SchedGlobals *gl,
+                 float *kernel_ms, const char *launch_what = "hipGetLastError()") {
+    Module &m = mod();
+    HX_HIP(hipEventRecord(m.ev0, m.stream));
+    HX_TRY(check_resident(kern, blocks, threads, 0, who));
+    launch();
+    return end_sched(who, gl, kernel_ms, launch_what);
+}
+
+// share of wave time spent inside batches
+inline double busy_frac(const SchedGlobals &gl) {
+    const double busy = (double)gl.counters[kCtrBusyCycles], idle = (double)gl.counters[kCtrIdleCycles];
+    return (busy + idle) > 0 ? busy / (busy + idle) : 0.0;
 }
 
 }  // namespace hx

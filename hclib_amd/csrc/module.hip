@@ -5,7 +5,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "hx_module.h"
+#include "hx_client.h"
 
 namespace hx {
 
@@ -417,8 +417,7 @@ int hclib_hip_sched_begin(uint32_t entry_words, uint32_t chunk, int waves_per_cu
     HX_TRY(ensure_device());
     Module &m = g_mod;
     PoolView pool;
-    HX_TRY(make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
-                     chunk, entry_words, &pool));
+    HX_TRY(sched_pool(64, chunk, entry_words, &pool));
     HX_TRY(reset_sched(pool, 1, false, (uint32_t)(m.num_cus * waves_per_cu)));
     HX_HIP(hipEventRecord(m.ev0, m.stream));
     out->hdr = pool.hdr;
@@ -441,12 +440,10 @@ int hclib_hip_sched_end(const char *who, uint64_t counters[16], uint64_t maxes[4
         set_error("hclib_hip_sched_end: no device");
         return HCLIB_HIP_ENODEV;
     }
-    HX_HIP(hipGetLastError());
-    HX_HIP(hipEventRecord(m.ev1, m.stream));
     SchedGlobals gl;
-    const int rc = finish_sched(&gl, who ? who : "hclib_hip_sched_end");
+    memset(&gl, 0, sizeof(gl));  // (a launch error returns before the read-back)
     float ms = 0;
-    (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
+    const int rc = end_sched(who ? who : "hclib_hip_sched_end", &gl, &ms);
     if (kernel_ms) *kernel_ms = ms;
     for (int i = 0; counters && i < 16; ++i) counters[i] = gl.counters[i];
     for (int i = 0; maxes && i < 4; ++i) maxes[i] = gl.maxes[i];

@@ -30,7 +30,7 @@
 
 #include <mutex>
 
-#include "hx_module.h"
+#include "hx_client.h"
 #include "../../include/hclib_hip/hx_finish.h"
 
 namespace hx {
@@ -402,14 +402,6 @@ int nq_plan(const char *who, int n, int form, int task_depth, bool count, NqPlan
     return HCLIB_HIP_OK;
 }
 
-template <class K>
-int nq_launch(const NqCtx &ctx, const PoolView &pool, const SchedConfig &cfg, int grid) {
-    Module &m = mod();
-    HX_TRY(check_resident((const void *)k_nqueens<K>, grid, 64, 0, "hclib_hip_nqueens"));
-    hipLaunchKernelGGL(k_nqueens<K>, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
-    return hip_check(hipGetLastError(), "hipLaunchKernelGGL(k_nqueens)");
-}
-
 }  // namespace
 
 extern "C" int hclib_hip_nqueens_bounds(int n, int form, int task_depth, uint64_t out[2]) {
@@ -437,8 +429,7 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
     HX_TRY(nq_plan("hclib_hip_nqueens", n, form, task_depth, bots, &p));
     HX_TRY(ensure_device());
     Module &m = mod();
-    const int grid = env_int("HCLIB_HIP_GRID", 0) > 0 ? env_int("HCLIB_HIP_GRID", 0)
-                                                    : m.num_cus * env_int("HCLIB_HIP_WAVES_PER_CU", 3);
+    const int grid = sched_grid(3);
     const int blocks = env_int("HCLIB_HIP_NQUEENS_BLOCKS", 1);
     if (bots && 1ull + (unsigned long long)grid * kScopeBlock > kNqIdReserve) {
         set_error("hclib_hip_nqueens: %d workers need more scope id blocks than the arena reserves", grid);
@@ -464,27 +455,17 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
     ctx.hist = hist ? (unsigned long long *)(dmem + jb + 256) : nullptr;
     HX_HIP(hipMemsetAsync(ctx.fin.next, 0, 256 + hb, m.stream));
     PoolView pool;
-    SchedConfig cfg;
-    HX_TRY(make_pool((uint32_t)env_int("HCLIB_HIP_DEQUES", 64), (uint32_t)env_int("HCLIB_HIP_DEQUE_CAP", 4096),
-                     (uint32_t)env_int("HCLIB_HIP_NQUEENS_CHUNK", 32), 8, &pool));
-    // fib's unseeded settings (fib.hip): a batch pushes at most 64 * 10
-    // range items, so 256 leaves the 1,024-item ring its room
-    cfg.spill_hi = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_HI", 256);
-    cfg.spill_lo = (uint32_t)env_int("HCLIB_HIP_NQUEENS_SPILL_LO", 32);
-    cfg.spin_limit = (uint32_t)env_int("HCLIB_HIP_SPIN_LIMIT_MS", 20000);
-    cfg.nwaves = (uint32_t)grid;
-    cfg.stamps = 0;
-    cfg.hunger = (uint32_t)env_int("HCLIB_HIP_NQUEENS_HUNGER", 8);
-    cfg.carry = (uint32_t)env_int("HCLIB_HIP_CARRY", 1);
+    HX_TRY(sched_pool(64, (uint32_t)env_int("HCLIB_HIP_NQUEENS_CHUNK", 32), 8, &pool));
+    const SchedConfig cfg = sched_config_unseeded("NQUEENS", grid);
     HX_TRY(reset_sched(pool, 1u, false, (uint32_t)grid));
-    HX_HIP(hipEventRecord(m.ev0, m.stream));
-    if (bots) HX_TRY(hist ? nq_launch<NqBotsKind<true>>(ctx, pool, cfg, grid)
-                          : nq_launch<NqBotsKind<false>>(ctx, pool, cfg, grid));
-    else HX_TRY(hist ? nq_launch<NqFlatKind<true>>(ctx, pool, cfg, grid)
-                     : nq_launch<NqFlatKind<false>>(ctx, pool, cfg, grid));
-    HX_HIP(hipEventRecord(m.ev1, m.stream));
+    void (*const kern)(NqCtx, PoolView, SchedGlobals *, SchedConfig) =
+        bots ? (hist ? k_nqueens<NqBotsKind<true>> : k_nqueens<NqBotsKind<false>>)
+             : (hist ? k_nqueens<NqFlatKind<true>> : k_nqueens<NqFlatKind<false>>);
     SchedGlobals gl;
-    HX_TRY(finish_sched(&gl, "hclib_hip_nqueens"));
+    float ms = 0;
+    HX_TRY(launch_sched((const void *)kern, grid, 64, "hclib_hip_nqueens", [&] {
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(64), 0, m.stream, ctx, pool, m.globals, cfg);
+    }, &gl, &ms, "hipLaunchKernelGGL(k_nqueens)"));
     unsigned long long v = 0, h[kNqMaxN + 1] = {};
     if (bots) HX_HIP(hipMemcpy(&v, ctx.fin.root_value, 8, hipMemcpyDeviceToHost));
     if (hist) HX_HIP(hipMemcpy(h, ctx.hist, 8 * (size_t)(n + 1), hipMemcpyDeviceToHost));
@@ -493,8 +474,6 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
         if (hipMemcpy(&used, ctx.fin.next, 4, hipMemcpyDeviceToHost) == hipSuccess)
             fprintf(stderr, "nqueens(%d): %u of %llu scope ids taken in HBM (local %d)\n", n, used, p.scopes, ctx.local);
     }
-    float ms = 0;
-    (void)hipEventElapsedTime(&ms, m.ev0, m.ev1);
     result->solutions = bots ? v : gl.counters[3];
     result->items = gl.counters[0];
     result->joins = gl.counters[1];
@@ -506,8 +485,7 @@ extern "C" int hclib_hip_nqueens(int n, int form, int task_depth, hclib_hip_nque
     result->chunks_pushed = gl.counters[kCtrPushed];
     result->chunks_stolen = gl.counters[kCtrStolen];
     result->kernel_ms = ms;
-    const double busy = (double)gl.counters[kCtrBusyCycles], idle = (double)gl.counters[kCtrIdleCycles];
-    result->busy_frac = (busy + idle) > 0 ? busy / (busy + idle) : 0.0;
+    result->busy_frac = busy_frac(gl);
     if (hist)
         for (int i = 0; i <= n; ++i) hist[i] = h[i];
     return HCLIB_HIP_OK;
