@@ -154,6 +154,14 @@ class JacobiResult(C.Structure):
                 ("kernel_ms", C.c_double), ("gbytes_per_s", C.c_double), ("gcells_per_s", C.c_double)]
 
 
+class BfsResult(C.Structure):
+    """hclib_hip_bfs_result_t."""
+
+    _fields_ = [("levels", C.c_uint64), ("reached", C.c_uint64), ("relaxed", C.c_uint64), ("items", C.c_uint64),
+                ("chunks_pushed", C.c_uint64), ("chunks_stolen", C.c_uint64),
+                ("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
+
+
 class HealthParams(C.Structure):
     """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
 
@@ -263,6 +271,7 @@ EXPORTS_HIP = [
     "hclib_hip_alignment_read_matrix", "hclib_hip_alignment_bounds", "hclib_hip_alignment_last_ticks",
     "hclib_hip_fft", "hclib_hip_fft_factors", "hclib_hip_fft_twiddles", "hclib_hip_fft_bounds", "hclib_hip_fft_last_ticks",
     "hclib_hip_jacobi", "hclib_hip_jacobi_rhs", "hclib_hip_jacobi_bounds",
+    "hclib_hip_bfs", "hclib_hip_bfs_bounds", "hclib_hip_bfs_read_input",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -378,6 +387,11 @@ def lib():
                                        C.c_int, C.c_void_p, C.POINTER(JacobiResult)]
         L.hclib_hip_jacobi_rhs.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.hclib_hip_jacobi_bounds.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_bfs.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                    C.POINTER(BfsResult), C.c_void_p, C.c_void_p]
+        L.hclib_hip_bfs_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                           C.POINTER(C.c_uint64)]
+        L.hclib_hip_bfs_read_input.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -1124,6 +1138,85 @@ def jacobi_bounds(nx: int, ny: int, block: int = 0, niter: int = 4, fuse: int = 
     out = (C.c_uint64 * 4)()
     _check(lib().hclib_hip_jacobi_bounds(nx, ny, block, niter, fuse, out), "hclib_hip_jacobi_bounds")
     return dict(zip(("tasks", "awaits", "supersteps", "bytes_moved"), out))
+
+
+# -------------------------------------------------------------- Rodinia BFS
+BFS_FORMS = {"level": 0, "async": 1}  # HCLIB_HIP_BFS_LEVEL / _ASYNC
+
+
+def _bfs_form(form) -> int:
+    if form not in BFS_FORMS:
+        raise ValueError(f"bfs: form {form!r} is not one of {sorted(BFS_FORMS)}")
+    return BFS_FORMS[form]
+
+
+def bfs_read_input(path) -> dict:
+    """A Rodinia BFS graph file (bfs.ref.cpp:84-121) through
+    hclib_hip_bfs_read_input, on the host alone: {"starting", "degree", "edges"
+    (int32 arrays), "source"}, as bfs() takes it. Nothing is checked here: the
+    launch and bfs_bounds refuse a graph that does not hold together."""
+    import numpy as np
+
+    counts = (C.c_int64 * 3)()
+    _check(lib().hclib_hip_bfs_read_input(os.fsencode(path), None, None, None, counts), "hclib_hip_bfs_read_input")
+    g = {"starting": np.empty(counts[0], dtype=np.int32), "degree": np.empty(counts[0], dtype=np.int32),
+         "edges": np.empty(counts[1], dtype=np.int32)}
+    _check(lib().hclib_hip_bfs_read_input(os.fsencode(path), g["starting"].ctypes.data, g["degree"].ctypes.data,
+                                          g["edges"].ctypes.data, counts), "hclib_hip_bfs_read_input")
+    g["source"] = int(counts[2])
+    return g
+
+
+def _bfs_graph(graph_or_path):
+    import numpy as np
+
+    g = bfs_read_input(graph_or_path) if isinstance(graph_or_path, (str, bytes, os.PathLike)) else graph_or_path
+    a = [np.ascontiguousarray(g[k], dtype=np.int32).ravel() for k in ("starting", "degree", "edges")]
+    if a[0].size != a[1].size:
+        raise ValueError("bfs: starting and degree must have one entry per vertex each")
+    return a[0], a[1], a[2], int(g["source"])
+
+
+def bfs(graph_or_path, form: str = "level", frontier: bool = False, order: bool = False) -> dict:
+    """Rodinia BFS on the work-stealing scheduler (hclib_hip_bfs): the hop count
+    of every vertex from the source, -1 where there is no path. graph_or_path: a
+    graph as bfs_read_input returns it, or a file of Rodinia's format. form
+    "level" follows the reference's level-by-level schedule over the frontier
+    alone, the wave that finishes a level last opening the next; "async" has no
+    levels and lowers costs with atomic minima until none changes. Returns the
+    fields of hclib_hip_bfs_result_t, "cost" (int32 array) and, on request,
+    "frontier" (vertices per level, `levels` entries) and "order" (level form:
+    the vertices in claiming order, level after level, -1 behind the reached)."""
+    import numpy as np
+
+    st, dg, ed, src = _bfs_graph(graph_or_path)
+    f = _bfs_form(form)
+    n = st.size
+    cost = np.empty(n, dtype=np.int32)
+    fr = np.zeros(n, dtype=np.uint64) if frontier else None
+    od = np.empty(n, dtype=np.int32) if order else None
+    r = BfsResult()
+    _check(lib().hclib_hip_bfs(st.ctypes.data, dg.ctypes.data, n, ed.ctypes.data if ed.size else None, ed.size, src, f,
+                               cost.ctypes.data, C.byref(r), fr.ctypes.data if frontier else None,
+                               od.ctypes.data if order else None), "hclib_hip_bfs")
+    out = {k: getattr(r, k) for k, _ in BfsResult._fields_}
+    out["cost"] = cost
+    if frontier:
+        out["frontier"] = [int(v) for v in fr[:r.levels]]
+    if order:
+        out["order"] = od
+    return out
+
+
+def bfs_bounds(graph_or_path, form: str = "level") -> dict:
+    """What a bfs() launch takes (hclib_hip_bfs_bounds), on the host alone: the
+    bytes of device memory and the bound n_nodes + n_edges on the level form's
+    items. Raises as the launch would for a graph it refuses."""
+    st, dg, ed, src = _bfs_graph(graph_or_path)
+    out = (C.c_uint64 * 2)()
+    _check(lib().hclib_hip_bfs_bounds(st.ctypes.data, dg.ctypes.data, st.size, ed.ctypes.data if ed.size else None,
+                                      ed.size, src, _bfs_form(form), out), "hclib_hip_bfs_bounds")
+    return {"arena_bytes": out[0], "items": out[1]}
 
 
 # --------------------------------------------------------------- BOTS Health

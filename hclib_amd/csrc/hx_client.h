@@ -2,8 +2,9 @@
 // run_dag_group clients (cholesky.hip, sparselu.hip) the version graph, the
 // one-promise Kind and the launch; run_dyn_worker clients (sort.hip,
 // strassen.hip, health.hip) the per-class counters, the timed Kind and the
-// launch; run_worker clients (fib.hip, nqueens.hip, floorplan.hip, uts.hip) the
-// grid and pool knobs, the unseeded SchedConfig, the launch and busy_frac.
+// launch; run_worker clients (fib.hip, nqueens.hip, floorplan.hip, uts.hip,
+// bfs.hip) the grid and pool knobs, the unseeded SchedConfig, the launch and
+// busy_frac.
 #pragma once
 
 #include <string.h>

@@ -83,6 +83,12 @@
  *                                    57-108), as neighbour awaits between block
  *                                    tasks of consecutive (time-fused) sweeps in
  *                                    one launch of the device promise DAG
+ *   hclib_hip_bfs                    the two hclib_forasync_future sweeps per level
+ *                                    and the hclib_future_wait after each of
+ *                                    Rodinia bfs (rodinia/bfs/bfs.cpp; bfs.ref.cpp:
+ *                                    139-182), as frontier items of the
+ *                                    work-stealing megakernel whose last finisher
+ *                                    opens the next level
  *   hclib_hip_atomic_*,            the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -1168,6 +1174,64 @@ int hclib_hip_jacobi(const double *f, const double *unew0, int nx, int ny, doubl
                      int block, int niter, int fuse, double *unew, hclib_hip_jacobi_result_t *result);
 int hclib_hip_jacobi_rhs(int nx, int ny, double *f, double *unew0);
 int hclib_hip_jacobi_bounds(int nx, int ny, int block, int niter, int fuse, uint64_t out[4]);
+
+/* Rodinia BFS (test/performance-regression/full-apps/rodinia/bfs/bfs.cpp; the
+ * algorithm as bfs.ref.cpp:135-183 states it): the hop count of every vertex
+ * from `source` over a directed graph in Rodinia's layout, vertex v owning
+ * edges[starting[v] .. starting[v] + degree[v]) (Node::starting and
+ * Node::no_of_edges, :32-36), as ONE launch of the work-stealing megakernel.
+ * cost[v] is the reference's h_cost: -1 where v is not reached (:128-131).
+ *   HCLIB_HIP_BFS_LEVEL  the reference's schedule, level by level (the do /
+ *       while of :139-182 with its two sweeps and the wait after each), made
+ *       work-efficient: a level is a range of `order`, the vertices in the
+ *       order they were claimed (h_graph_visited and h_updating_graph_mask in
+ *       one), a vertex of the level is an item whose children are its edges,
+ *       an edge claims its head with one compare-and-swap on cost. No wave
+ *       waits for a level to end: every wave counts the items it ran, and the
+ *       wave whose count completes the level opens the next (the scheduler's
+ *       renew hook, include/hclib_hip/hx_sched.h).
+ *   HCLIB_HIP_BFS_ASYNC  no levels: an edge lowers cost[head] with an atomic
+ *       minimum and a strict lowering makes head's edges items again; an item
+ *       whose vertex has since got a lower cost does nothing. The same cost
+ *       array bit for bit, at the price of the edges relaxed more than once.
+ * result: levels = the reference's sweep count k (:180), the eccentricity of
+ * the source + 1; reached = vertices with cost >= 0; relaxed = edge items that
+ * ran their atomic (level form: the degrees of the reached vertices summed);
+ * items = every item run (level form: reached + relaxed; async form: 1 +
+ * relaxed + the edge items that found their vertex out of date).
+ * frontier (may be NULL): n_nodes words, frontier[L] = vertices at cost L, 0
+ * from `levels` on. order (may be NULL, level form only): n_nodes words, the
+ * reached vertices level after level, within a level in claiming order (which
+ * differs from run to run), the rest -1.
+ * EINVAL, before the device is touched, where the reference's behaviour is
+ * undefined: a NULL array (edges may be NULL when n_edges is 0), n_nodes < 1
+ * or >= 2^24, n_edges < 0, source outside [0, n_nodes), a degree < 0 or
+ * >= 2^24, starting[v] < 0 or starting[v] + degree[v] > n_edges, an edge head
+ * outside [0, n_nodes), an unknown form, order with the async form.
+ * The launch reads HCLIB_HIP_BFS_CHUNK (items per stolen chunk, 32) and the
+ * scheduler's HCLIB_HIP_BFS_SPILL_HI / _SPILL_LO / _HUNGER.
+ * hclib_hip_bfs_bounds: host only, with the same checks: out[0] = the bytes of
+ * device memory the form takes, out[1] = n_nodes + n_edges, which no launch's
+ * level-form item count exceeds.
+ * hclib_hip_bfs_read_input: host only: Rodinia's text format read as the
+ * reference's fscanf sequence reads it (:84-121): the node count, a (start,
+ * degree) pair per node, the source, the edge count, an (id, weight) pair per
+ * edge with the weight dropped. With every array NULL it only sizes: counts[0]
+ * = nodes, counts[1] = edges, counts[2] = source. Otherwise the arrays have
+ * the sizes a first call reported (EINVAL if the file's counts differ). */
+typedef struct {
+    uint64_t levels, reached, relaxed, items, chunks_pushed, chunks_stolen;
+    double kernel_ms, busy_frac;
+} hclib_hip_bfs_result_t;
+#define HCLIB_HIP_BFS_LEVEL 0
+#define HCLIB_HIP_BFS_ASYNC 1
+int hclib_hip_bfs(const int32_t *starting, const int32_t *degree, int n_nodes, const int32_t *edges, int n_edges,
+                  int source, int form, int32_t *cost, hclib_hip_bfs_result_t *result,
+                  uint64_t *frontier /* n_nodes entries, may be NULL */,
+                  int32_t *order /* n_nodes entries, may be NULL; level form */);
+int hclib_hip_bfs_bounds(const int32_t *starting, const int32_t *degree, int n_nodes, const int32_t *edges,
+                         int n_edges, int source, int form, uint64_t out[2]);
+int hclib_hip_bfs_read_input(const char *path, int32_t *starting, int32_t *degree, int32_t *edges, int64_t counts[3]);
 
 #ifdef __cplusplus
 }

@@ -305,6 +305,8 @@ struct SchedConfig {
 //                                     // (process gets `valid`; invalid lanes'
 //                                     // results are dropped)
 //   static constexpr bool kBoundedChildren;  // process() never returns >= kMaxChildren
+//   optional: drain (kind_has_drain) and renew (kind_has_renew), both called by
+//   the whole wave where its ring has run empty
 //   optional, pure kinds only:
 //   __device__ static void process2(const Ctx&, Acc&, const uint32_t *tmplA, uint32_t kA,
 //                                   uint32_t *childA, int &ncA, const uint32_t *tmplB,
@@ -597,6 +599,14 @@ template <class K, class = void>
 struct kind_has_drain : std::false_type {};
 template <class K>
 struct kind_has_drain<K, decltype((void)&K::drain)> : std::true_type {};
+// Optional: static int renew(const Ctx&, Acc&, uint32_t *tmpl), whole wave,
+// uniform control flow: called where an active wave's ring has run empty,
+// after drain. n > 0: tmpl is a new root template with n children, which the
+// wave pushes as it pushes Kind::roots, staying active; 0: the wave goes idle
+template <class K, class = void>
+struct kind_has_renew : std::false_type {};
+template <class K>
+struct kind_has_renew<K, decltype((void)&K::renew)> : std::true_type {};
 template <class Kind>
 __device__ __forceinline__ void kind_drain(const typename Kind::Ctx &ctx, typename Kind::Acc &acc, uint32_t *err) {
     if constexpr (kind_has_drain<Kind>::value) Kind::drain(ctx, acc, err);
@@ -1812,6 +1822,25 @@ __device__ uint32_t seed_levels(const typename Kind::Ctx &ctx, typename Kind::Ac
     return n;
 }
 
+// A root template with n children (wave-uniform) as the only items of an
+// empty ring, at positions 0 ..: Kind::roots at the start of a launch,
+// Kind::renew where a ring ran empty. Returns the items pushed (the new top);
+// the caller moves `tag` on by 16.
+template <class Kind, int CAP>
+__device__ __forceinline__ uint32_t push_root(WaveStack<Kind, CAP> &st, uint32_t *err, const uint32_t *tmpl, int n,
+                                              int lane, uint32_t tag) {
+    constexpr int kPieces = pieces_of<Kind>();
+    uint32_t ucnt = lane == 0 && n > 0 ? (uint32_t)n : 0u;
+    if (ucnt >= kMaxChildren) {
+        dev_error(err, kErrBadTask);
+        ucnt = 0;
+    }
+    const uint32_t nch = ucnt > (uint32_t)kPieces ? (uint32_t)kPieces : ucnt;
+    const uint32_t tout = lane0(nch);
+    push_outputs<Kind, CAP>(st, 0, 0, tout, 0, ucnt, nch, tmpl, tmpl, 0, 0, tag);
+    return tout;
+}
+
 // GLOBAL: the launch shares work with the other ranks through g->gview
 // (idle waves take chunks from the global ring, a wave holding spill_lo+
 // items exports a chunk while some rank is idle and none of its own waves
@@ -1920,14 +1949,7 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
     if (seed_roots && !seeded) {
         uint32_t tmpl[TW];
         const int n = Kind::roots(ctx, acc, tmpl);  // uniform across the wave
-        uint32_t ucnt = lane == 0 && n > 0 ? (uint32_t)n : 0u;
-        if (ucnt >= kMaxChildren) {
-            dev_error(&g->err, kErrBadTask);
-            ucnt = 0;
-        }
-        const uint32_t nch = ucnt > (uint32_t)kPieces ? (uint32_t)kPieces : ucnt;
-        const uint32_t tout = lane0(nch);
-        push_outputs<Kind, CAP>(st, 0, 0, tout, 0, ucnt, nch, tmpl, tmpl, 0, 0, tag);
+        const uint32_t tout = push_root<Kind, CAP>(st, &g->err, tmpl, n, lane, tag);
         tag += 16;
         top = tout;
         active = true;  // the host initialised outstanding = 1 for this wave
@@ -1980,6 +2002,27 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
             }
             if (active) {
                 kind_drain<Kind>(ctx, acc, &g->err);
+                if constexpr (kind_has_renew<Kind>::value) {
+                    // the device form of help_finish (src/hclib-runtime.c): the
+                    // wave that finishes a phase last runs what follows it. It
+                    // stays active and keeps its unit of `outstanding`
+                    uint32_t tmpl[TW];
+                    const int rn = Kind::renew(ctx, acc, tmpl);  // uniform across the wave
+                    if (rn > 0) {
+                        bot = 0;
+                        top = push_root<Kind, CAP>(st, &g->err, tmpl, rn, lane, tag);
+                        tag += 16;
+                        if (top) {
+                            tl.log(kTlBusy, top);
+                            const unsigned long long now = __builtin_amdgcn_s_memtime();
+                            lds_sum(st, 1, now - t_mark);
+                            t_mark = now;
+                            t_batch = now;
+                            busy_phase = true;
+                            continue;
+                        }
+                    }
+                }
                 active = false;
                 wave_goes_idle<GLOBAL>(g, gv, pool);
                 tl.log(kTlIdle, 0);
