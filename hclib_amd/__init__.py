@@ -256,7 +256,7 @@ EXPORTS_HIP = [
     "hclib_hip_num_workers", "hclib_hip_uts_search", "hclib_hip_uts_num_children_host",
     "hclib_hip_uts_bucket_check", "hclib_hip_sha1_calibrate",
     "hclib_hip_fib", "hclib_hip_sw", "hclib_hip_last_sched_counters", "hclib_hip_last_narrow_counters",
-    "hclib_hip_last_phase_counters", "hclib_hip_last_shed_counters",
+    "hclib_hip_last_phase_counters", "hclib_hip_last_shed_counters", "hclib_hip_last_comm_counters",
     "hclib_hip_sw_band_begin", "hclib_hip_sw_band_rows", "hclib_hip_sw_band_end",
     "hclib_hip_sw_edges", "hclib_hip_sw_band_bottoms",
     "hclib_hip_atomic_create", "hclib_hip_atomic_destroy", "hclib_hip_atomic_view",
@@ -1522,6 +1522,17 @@ def last_shed_counters():
     out = (C.c_uint64 * 8)()
     lib().hclib_hip_last_shed_counters(out)
     return dict(zip(("exits", "placed", "blocks", "items", "fallbacks"), out))
+
+
+def last_comm_counters():
+    """The hand-off waves' counts of the last launch (hclib_hip_last_comm_counters):
+    the outbox blocks and items of the main loop's give-away and of the narrow
+    loop's overflow exit, the blocks passed on to a deque and to a sibling,
+    the claims that found no outbox free, the overflow exits that reached the ring."""
+    out = (C.c_uint64 * 8)()
+    lib().hclib_hip_last_comm_counters(out)
+    return dict(zip(("main_blocks", "main_items", "shed_blocks", "shed_items", "to_deque", "to_sibling", "busy",
+                     "ring_exits"), out))
 
 
 TIMELINE_EVENTS = {1: "start", 2: "busy", 3: "idle", 4: "spill", 5: "term", 6: "end"}

@@ -58,6 +58,8 @@ struct Module {
     unsigned long long last_counters[16] = {};  // counters of the last megakernel launch
     unsigned long long last_narrow[4] = {};     // SchedGlobals::narrow of the last launch
     unsigned long long last_shed[8] = {};       // SchedGlobals::shed of the last launch
+    unsigned long long last_comm[8] = {};       // the hand-off waves' counts of the last launch (hx_sched.h kComm*)
+    int comm_wpg = 0;  // the next launch has hand-off waves: its workgroups' worker waves (finish_sched reads and clears)
     unsigned long long last_phase[8] = {};     // HX_PHASES builds (hclib_hip_last_phase_counters)
     // per-wave records of megakernel launches (WaveStat, hx_sched.h)
     WaveStat *wave_stats = nullptr;

@@ -48,7 +48,29 @@ struct UtsKnobs {
     int hunger = kUnset;         // 32, 64 on BIN trees, 128 on large fixed-shape ones
     int spin_limit_ms = 20000, stamps = 0, carry = 2, backoff = 16, defer = 1, spills_per_batch = 0;
     int narrow_shed = 1, narrow_shed_sibs = 3;
+    // the hand-off wave of a BIN workgroup and the users of its outbox (bits:
+    // 1 the give-away loop, 2 narrow_shed's leftovers, 4 the wave's redirect
+    // to a sibling gone idle; 0: no such wave, workgroups of 64 x wpg threads).
+    // 2: T3L 25.60 -> 24.59 ms against 0, medians of six interleaved rounds; 1
+    // alone 25.82, 3 24.54, 6 24.65, 7 24.65 (profiles/r23/ab_comm_knob_t3l.log):
+    // bits 1 and 4 show no gain and stay off
+    int uts_comm = 2;
 };
+
+// waves in a workgroup of k_uts_search<..., global, wpg> at most: the worker
+// waves and, where the kernel can run one, the hand-off wave
+constexpr int uts_block_waves(int wpg, bool global) { return wpg + (wpg > 1 && !global ? 1 : 0); }
+
+// HCLIB_HIP_UTS_COMM is a set of three bits
+inline bool uts_comm_valid(int comm, std::string &err) {
+    if (comm >= 0 && comm <= 7) return true;
+    char buf[160];
+    snprintf(buf, sizeof(buf),
+             "hclib_hip_uts_search: HCLIB_HIP_UTS_COMM=%d is not a set of the outbox's users (0..7: 1 give-away, 2 "
+             "narrow shed, 4 redirect)", comm);
+    err = buf;
+    return false;
+}
 
 struct UtsPlan {
     int status = HCLIB_HIP_OK;  // HCLIB_HIP_EINVAL: a knob or the trace was refused (`err` says why)
@@ -67,6 +89,12 @@ struct UtsPlan {
     // SchedConfig, member by member
     uint32_t spill_hi = 0, spill_lo = 0, spin_limit = 0, nwaves = 0, stamps = 0, hunger = 0, backoff = 0, carry = 0,
              defer = 0, dual = 0, spills = 0, hunger_init_full = 0, narrow_shed = 0;
+    // ... with `comm` in bits 16..18 of its narrow_shed: the hand-off wave's
+    // users (UtsKnobs::uts_comm), 0 where the launch has no such wave; `block`
+    // = the threads of a workgroup, 64 x (wpg + 1) with the wave and 64 x wpg
+    // without (grid and wpg count worker waves either way)
+    uint32_t comm = 0;
+    int block = 64;
     // SeedCfg (target 0: unseeded)
     uint32_t seed_target = 0, seed_max_levels = 0, seed_min_levels = 0, seed_solo_cap = 0;
     // what hclib_hip_uts_last_launch reports
@@ -93,6 +121,10 @@ inline UtsPlan uts_plan(const hclib_hip_uts_params_t &p, const UtsTables &T, int
     constexpr int U = UtsKnobs::kUnset;
     (void)shard;  // every shard of a search takes the same shape
     UtsPlan P;
+    if (!uts_comm_valid(kn.uts_comm, err)) {
+        P.status = HCLIB_HIP_EINVAL;
+        return P;
+    }
     const int trace_kind = max_levels > 0 ? kn.uts_trace : 0;
     const bool trace = trace_kind != 0;
 
@@ -408,6 +440,14 @@ inline UtsPlan uts_plan(const hclib_hip_uts_params_t &p, const UtsTables &T, int
         if (P.wpg != 2 && P.wpg != 4) P.wpg = 1;
         if (grid % P.wpg) P.wpg = 1;
     }
+    // the hand-off wave: where the workgroup has siblings to hand off for and
+    // the kernel can run one (uts_block_waves: never a launch that shares
+    // across ranks; the depth trace runs lone waves, the chain stamps keep it)
+    if (P.wpg > 1 && uts_block_waves(P.wpg, global) > P.wpg) P.comm = (uint32_t)kn.uts_comm;
+    // (narrow_shed fills a block with up to one batch of items, and the wave
+    // enqueues a block as one chunk: with smaller chunks that user stays off)
+    if (kn.chunk < 64) P.comm &= ~2u;
+    P.block = 64 * (P.wpg + (P.comm ? 1 : 0));
     P.launch = hclib_hip_uts_launch_t{mode, trace ? 1 + trace_kind : P.feat, P.wpg, grid, P.ring, P.seed_target ? 1 : 0, (int)P.seed_target,
                                       (int)P.spill_lo, P.waves_per_cu};
     return P;

@@ -280,6 +280,9 @@ int finish_sched(SchedGlobals *host_copy, const char *who) {
             if (r[16 + i] > host_copy->maxes[i]) host_copy->maxes[i] = r[16 + i];
         for (int i = 0; i < 3; ++i) host_copy->narrow[i] += r[20 + i];
         for (int i = 0; i < kShedCounts; ++i) host_copy->shed[i] += r[32 + i];
+        // the hand-off counts of a workgroup: in the records of its first two workers
+        if (m.comm_wpg > 1 && w % (uint32_t)m.comm_wpg < 2)
+            for (int i = 0; i < 3; ++i) host_copy->comm[3 * (w % (uint32_t)m.comm_wpg) + i] += r[37 + i];
         m.last_phase[0] += r[23];
         for (int i = 0; i < 4; ++i) m.last_phase[1 + i] += r[28 + i];
         m.last_phase[5] += r[24];  // HX_PHASES builds only (else the stamps' push cycles)
@@ -288,6 +291,14 @@ int finish_sched(SchedGlobals *host_copy, const char *who) {
     memcpy(m.last_counters, host_copy->counters, sizeof(m.last_counters));
     memcpy(m.last_narrow, host_copy->narrow, sizeof(m.last_narrow));
     memcpy(m.last_shed, host_copy->shed, sizeof(m.last_shed));
+    {
+        // CommCtl::cnt, unpacked into the kComm* order
+        const unsigned long long *c = host_copy->comm;
+        const unsigned long long u[kCommCounts] = {c[0] & 0xffffffffull, c[0] >> 32, c[1] & 0xffffffffull, c[1] >> 32,
+                                                   c[2], c[3], c[4], c[5]};
+        memcpy(m.last_comm, u, sizeof(m.last_comm));
+        m.comm_wpg = 0;
+    }
     // every wave of the grid leaves exactly once: counters[kCtrWaves] records
     uint64_t nw = host_copy->counters[kCtrWaves];
     if (nw > nw_cap) nw = nw_cap;
@@ -391,6 +402,10 @@ void hclib_hip_last_narrow_counters(uint64_t out[4]) {
 
 void hclib_hip_last_shed_counters(uint64_t out[8]) {
     for (int i = 0; i < 8; ++i) out[i] = g_mod.last_shed[i];
+}
+
+void hclib_hip_last_comm_counters(uint64_t out[8]) {
+    for (int i = 0; i < 8; ++i) out[i] = g_mod.last_comm[i];
 }
 
 int hclib_hip_last_wave_stats(hclib_hip_wave_stats_t *out, int max) {

@@ -347,20 +347,35 @@ struct UtsKind {
 // GLOBAL: a sharded launch that shares work with the other ranks
 // (hclib_hip_global_attach; hx_sched.h GlobalView). WPG: worker waves per
 // workgroup, handing work to idle siblings through LDS inboxes (hx_sched.h
-// Inbox) before the HBM deques.
+// Inbox) before the HBM deques. Such a workgroup (not GLOBAL) may be launched
+// with 64 more threads: wave WPG is then its hand-off wave (hx_sched.h
+// comm_wave), which runs no task and is no worker of the grid.
 template <int MODE, int FEAT, int CAP = (MODE == kUtsBin ? 1024 : 512), bool GLOBAL = false, int WPG = 1>
-__global__ __launch_bounds__(64 * WPG) void k_uts_search(UtsCtx ctx, PoolView pool, SchedGlobals *g,
-                                                         SchedConfig cfg) {
+__global__ __launch_bounds__(64 * uts_block_waves(WPG, GLOBAL)) void k_uts_search(UtsCtx ctx, PoolView pool,
+                                                                                  SchedGlobals *g, SchedConfig cfg) {
     constexpr int kUtsCap = CAP;
+    constexpr bool kComm = uts_block_waves(WPG, GLOBAL) > WPG;
     using K = UtsKind<MODE, FEAT, CAP>;
     __shared__ WaveStack<K, kUtsCap> st[WPG];
-    __shared__ Inbox<K> ib[WPG];
+    __shared__ WgBoxes<K, WPG> bx;
+    static_assert(sizeof(st) + sizeof(bx) + (MODE == kUtsBin ? 0 : sizeof(s_rules) + sizeof(s_thr)) <= 160 * 1024,
+                  "a workgroup's rings, boxes and rule tables fit a CU's LDS");
+    Inbox<K> *ib = bx.ib;
     const uint32_t wave = WPG > 1 ? threadIdx.x / 64 : 0;
     const uint32_t worker = blockIdx.x * WPG + wave;
     if (WPG > 1) {
         if (threadIdx.x < WPG) {
             ib[threadIdx.x].state = 0;
             ib[threadIdx.x].idle = 0;
+        }
+    }
+    if constexpr (WPG > 1) {
+        if (threadIdx.x < kOutboxes) bx.out[threadIdx.x].state = 0;
+        if (threadIdx.x < 6) bx.ctl.cnt[threadIdx.x] = 0;
+        if (threadIdx.x == 0) {
+            // the outbox has users only where the launch brought the wave
+            bx.ctl.on = kComm && blockDim.x > 64u * WPG ? (cfg.narrow_shed >> 16) & 7u : 0u;
+            bx.ctl.left = 0;
         }
     }
     if (MODE == kUtsGeoFixed) {
@@ -374,7 +389,17 @@ __global__ __launch_bounds__(64 * WPG) void k_uts_search(UtsCtx ctx, PoolView po
         for (int i = threadIdx.x; i < ctx.nthr; i += 64 * WPG) s_thr[i] = ctx.thr[i];
     }
     __syncthreads();
+    if constexpr (kComm) {
+        if (wave == (uint32_t)WPG) {
+            comm_wave<K, kUtsCap, WPG>(ctx, pool, g, cfg, bx, st[0]);
+            return;
+        }
+    }
     run_worker<K, kUtsCap, GLOBAL, WPG>(ctx, pool, g, cfg, st[wave], worker == 0, ib, wave, worker);
+    if constexpr (kComm) {
+        if (threadIdx.x % 64 == 0)
+            __hip_atomic_fetch_add((hx_lds_u32 *)&bx.ctl.left, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    }
 }
 
 // build_tables, its error (if any) reported through set_error
@@ -492,6 +517,7 @@ static UtsKnobs uts_knobs() {
     k.spills_per_batch = env_int("HCLIB_HIP_SPILLS_PER_BATCH", k.spills_per_batch);
     k.narrow_shed = env_int("HCLIB_HIP_NARROW_SHED", k.narrow_shed);
     k.narrow_shed_sibs = env_int("HCLIB_HIP_NARROW_SHED_SIBS", k.narrow_shed_sibs);
+    k.uts_comm = env_int("HCLIB_HIP_UTS_COMM", k.uts_comm);
     return k;
 }
 
@@ -539,6 +565,14 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
         max_levels > (knobs.uts_trace == 2 ? 4 * 65536 : 65536) || (nshards > 1 && split_depth < 1)) {
         set_error("hclib_hip_uts_search: invalid arguments");
         return HCLIB_HIP_EINVAL;
+    }
+    {
+        // (a knob the plan would refuse, refused before the tables' arena is reserved)
+        std::string why;
+        if (!uts_comm_valid(knobs.uts_comm, why)) {
+            set_error("%s", why.c_str());
+            return HCLIB_HIP_EINVAL;
+        }
     }
     HX_TRY(ensure_device());
     Module &m = mod();
@@ -646,15 +680,18 @@ extern "C" int hclib_hip_uts_search(const hclib_hip_uts_params_t *params, int sh
     cfg.dual = plan.dual;
     cfg.spills = plan.spills;
     cfg.hunger_init_full = plan.hunger_init_full;
-    cfg.narrow_shed = plan.narrow_shed;
+    cfg.narrow_shed = plan.narrow_shed | plan.comm << 16;
     SeedCfg seed{plan.seed_target, plan.seed_max_levels, (uint32_t)UtsKind<kUtsBin, 0>::kWords, plan.seed_min_levels};
     seed.solo_cap = plan.seed_solo_cap;
     HX_TRY(reset_sched(pool, 1, plan.global, (uint32_t)plan.grid, seed.target ? &seed : nullptr));
     g_last_launch = plan.launch;
     SchedGlobals gl;
     float ms = 0;
-    const int rc = launch_sched((const void *)kern, plan.grid / plan.wpg, 64 * plan.wpg, who, [&] {
-        hipLaunchKernelGGL(kern, dim3(plan.grid / plan.wpg), dim3(64 * plan.wpg), 0, m.stream, ctx, pool, m.globals, cfg);
+    // (the hand-off waves are in plan.block, not in the grid: they hold no
+    // work, have no exit record and are no wave of SchedConfig::nwaves)
+    m.comm_wpg = plan.comm ? plan.wpg : 0;
+    const int rc = launch_sched((const void *)kern, plan.grid / plan.wpg, plan.block, who, [&] {
+        hipLaunchKernelGGL(kern, dim3(plan.grid / plan.wpg), dim3(plan.block), 0, m.stream, ctx, pool, m.globals, cfg);
     }, &gl, &ms);
     if (rc != HCLIB_HIP_OK) return rc;
     if (max_levels) {

@@ -173,6 +173,15 @@ void hclib_hip_last_narrow_counters(uint64_t out[4]);
  * inboxes (the loop went on), [2] inboxes filled, [3] items in them, [4]
  * exits that left children for the ring and the main loop; [0] = [1] + [4]. */
 void hclib_hip_last_shed_counters(uint64_t out[8]);
+/* The hand-off waves of the last megakernel launch (hx_sched.h comm_wave; UTS
+ * BIN workgroups with HCLIB_HIP_UTS_COMM != 0, zeros otherwise): [0] outbox
+ * blocks filled by the main loop's give-away, [1] items in them, [2] outbox
+ * blocks filled by the narrow loop's overflow exit, [3] items in them, [4]
+ * blocks the hand-off waves enqueued to an HBM deque, [5] blocks they copied
+ * to a sibling that had gone idle ([0] + [2] = [4] + [5]), [6] give-aways and
+ * exits that found no outbox free, [7] overflow exits that still left
+ * children for the ring. */
+void hclib_hip_last_comm_counters(uint64_t out[8]);
 /* Diagnostic (HX_PHASES builds, zeros otherwise): [0] main-loop single
  * batches of the last megakernel launch, [1..4] their s_memtime cycles from
  * loop top to pop issued, pop landed, body done, batch end. */

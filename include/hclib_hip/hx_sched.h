@@ -159,6 +159,9 @@ struct alignas(256) SchedGlobals {
         uint32_t solo_cap;     // wave 0 runs levels of at most this many slots alone (0: the ring's room)
     } seed;
     unsigned long long shed[8];  // narrow-loop overflow sheds (kShed* below), summed over the waves
+    // the hand-off waves' counts (CommCtl::cnt, packed as there) of workers
+    // that have no exit record
+    unsigned long long comm[8];
 };
 constexpr int kSeedMaxLevels = 24;
 constexpr int kSeedGoLines = 64;  // "level d is complete" broadcast lines (a wave polls line gid % 64)
@@ -166,7 +169,9 @@ constexpr int kSeedCtlLines = 2 * kSeedMaxLevels + 2 + kSeedGoLines;
 // a worker's exit record: [0..7] the kind's counters, [8..15] the
 // scheduler's counters (SchedGlobals::counters [8..15]; [4..7] of the
 // diagnostic stamps go to [24..27]), [16..19] the kind's maxima, [20..22]
-// the narrow-loop counts, [32..36] the narrow-loop overflow sheds (kShed*)
+// the narrow-loop counts, [32..36] the narrow-loop overflow sheds (kShed*),
+// [37..39] the workgroup's hand-off counts (CommCtl::cnt [0..2] in the record
+// of its wave 0, [3..5] in that of its wave 1; 0 in the others)
 constexpr int kWaveCtrWords = 40;
 // narrow-loop overflow exits of a wave with siblings (narrow_shed; all 0 with
 // SchedConfig::narrow_shed off): every exit is either placed or a fallback
@@ -177,6 +182,25 @@ enum : int {
     kShedItems = 3,      // items in them
     kShedFallbacks = 4,  // exits with spawners left over (onto the ring, back to the main loop)
     kShedCounts = 5,
+};
+// the hand-off wave and its outbox (comm_wave; all 0 without one), as
+// hclib_hip_last_comm_counters reports them
+enum : int {
+    kCommMainBlocks = 0,  // outbox blocks filled by the main loop's give-away
+    kCommMainItems = 1,   // items in them
+    kCommShedBlocks = 2,  // outbox blocks filled by narrow_shed
+    kCommShedItems = 3,   // items in them
+    kCommToDeque = 4,     // blocks the hand-off wave enqueued to an HBM deque
+    kCommToSibling = 5,   // blocks it copied into the inbox of a sibling that had gone idle
+    kCommBusy = 6,        // give-aways and shed exits that found no outbox free
+    kCommRing = 7,        // narrow-loop overflow exits that still reached the ring
+    kCommCounts = 8,
+};
+// SchedConfig::narrow_shed bits 16..18 (HCLIB_HIP_UTS_COMM): who uses the outbox
+enum : uint32_t {
+    kCommUseMain = 1,      // run_worker's give-away loop
+    kCommUseShed = 2,      // narrow_shed's leftover spawners
+    kCommUseRedirect = 4,  // the hand-off wave looks for a sibling gone idle before the deques
 };
 
 // Diagnostic build (-DHX_TIMELINE=1, `python -m hclib_amd.build --variant
@@ -281,7 +305,9 @@ struct SchedConfig {
     // (narrow_shed; read only there). Bits 0..7: 0 = every child onto the ring
     // and back to the main loop; else the spawners the wave keeps as its next
     // level: 1 = half, 2 = as many as fit one batch, 3 = a quarter (each
-    // capped at one batch). Bits 8..15: sibling inboxes one exit may fill
+    // capped at one batch). Bits 8..15: sibling inboxes one exit may fill.
+    // Bits 16..18 (kCommUse*): the users of the workgroup's hand-off wave, 0 =
+    // the launch has none (its workgroups are 64 * WPG threads, else 64 more)
     uint32_t narrow_shed = 0;
 };
 
@@ -623,10 +649,16 @@ __device__ __forceinline__ void kind_drain(const typename Kind::Ctx &ctx, typena
 // enqueue. (`pc` is a reference, never a pointer that may be null: a
 // select between a local's address and null keeps the local in scratch
 // memory, and every batch then read its `live` flag behind a vmcnt(0) wait.)
-template <class Kind, int CAP>
+// The hand-off wave (comm_wave) enqueues an outbox block instead: BLOCK = the
+// n items are the packed words of `blk` (an Inbox's, already exported and
+// stamped by the wave that filled it), `st` and `bot` unread; HELD = the
+// chunk's unit of `outstanding` was taken when the block was filled.
+template <class Kind>
+struct Inbox;
+template <class Kind, int CAP, bool BLOCK = false, bool HELD = false>
 __device__ bool enqueue_chunk(const typename Kind::Ctx &ctx, const PoolView &pool, SchedGlobals *g, uint32_t q,
                               WaveStack<Kind, CAP> &st, uint32_t bot, uint32_t n, uint32_t &occ, PendingChunk &pc,
-                              bool defer, bool relief = false) {
+                              bool defer, bool relief = false, const Inbox<Kind> *blk = nullptr) {
     constexpr int W = Kind::kWords;
     const int lane = lane_id();
     QueueHdr *h = &pool.hdr[q];
@@ -634,7 +666,11 @@ __device__ bool enqueue_chunk(const typename Kind::Ctx &ctx, const PoolView &poo
     // go out before the ticket's round trip, which then hides them
     const bool valid = (uint32_t)lane < n;
     uint32_t w[W];
-    {
+    if constexpr (BLOCK) {
+        const hx_lds_u32 *src = (const hx_lds_u32 *)&blk->w[(valid ? (uint32_t)lane : 0u) * W];
+#pragma unroll
+        for (int i = 0; i < W; ++i) w[i] = src[i];
+    } else {
         const uint32_t p = bot + (valid ? (uint32_t)lane : 0u);
         const uint2 dd = st.d[p & (CAP - 1)];
         load_tmpl<Kind, CAP>(st, (p - (dd.y >> 24)) & (CAP - 1), w);
@@ -646,7 +682,7 @@ __device__ bool enqueue_chunk(const typename Kind::Ctx &ctx, const PoolView &poo
     const bool fast = occ < pool.cap / 4;
     if (lane == 0) {
         if (fast) {
-            add_agent(&g->outstanding, 1u);  // counts before it becomes visible
+            if (!HELD) add_agent(&g->outstanding, 1u);  // counts before it becomes visible
             pos = add_agent(&h->tail, 1u);
             seen = pos - ld_agent(&h->head);
             ok = 1;
@@ -659,7 +695,7 @@ __device__ bool enqueue_chunk(const typename Kind::Ctx &ctx, const PoolView &poo
             // The ticket is taken by CAS on the tail it checked, so concurrent
             // producers cannot together push it past that bound
             if ((int)(tl - hd) < (int)(relief ? pool.cap - 1 : pool.cap / 2) && cas_agent(&h->tail, tl, tl + 1u)) {
-                add_agent(&g->outstanding, 1u);  // before the chunk is published
+                if (!HELD) add_agent(&g->outstanding, 1u);  // before the chunk is published
                 pos = tl;
                 ok = 1;
             }
@@ -682,8 +718,10 @@ __device__ bool enqueue_chunk(const typename Kind::Ctx &ctx, const PoolView &poo
     }
     uint32_t *dst = pool.data + (size_t)slot * pool.chunk * W;
     {
-        kind_export<Kind>(ctx, w, valid, &g->err);
-        kind_trace_item<Kind>(ctx, w, valid, 2u, false);
+        if constexpr (!BLOCK) {
+            kind_export<Kind>(ctx, w, valid, &g->err);
+            kind_trace_item<Kind>(ctx, w, valid, 2u, false);
+        }
         if (valid) {
             if constexpr (W % 4 == 0) {
                 // 16-byte sc1 stores (a dword sc1 store costs ~6x the bytes of
@@ -1386,6 +1424,53 @@ struct Inbox {
     uint32_t w[64 * Kind::kWords];
 };
 
+// The hand-off ("comm") wave of a workgroup (comm_wave below): wave WPG of a
+// block of 64 * (WPG + 1) threads, which never runs a task. A worker that has
+// items to give and no idle sibling claims an outbox (an Inbox-shaped block,
+// the same CAS and fill, the block's unit of `outstanding` taken at the fill)
+// and goes back to its tasks having paid LDS traffic only; the comm wave
+// passes the block on, to a sibling that has gone idle since or as a chunk
+// to the HBM deques, and pays the deque's round trips itself.
+// Two outboxes: one overflow exit of the narrow loop (narrow_shed) often has
+// more than one batch of children left after the siblings, and two workers
+// of four give at once while the comm wave is inside an enqueue's round
+// trips (~2 us, against ~1.3 us per level of a giving chain); two keep
+// either case in LDS for 2 KiB apiece. More would only queue blocks behind
+// one wave's serial enqueues, and the deques take what finds no outbox.
+constexpr int kOutboxes = 2;
+struct CommCtl {
+    uint32_t on;    // kCommUse* of this launch (0: the workgroup has no comm wave)
+    uint32_t left;  // workers that have left the megakernel
+    // the workgroup's counts: [0] kCommMainBlocks | kCommMainItems << 32, [1]
+    // kCommShedBlocks | kCommShedItems << 32, [2] kCommToDeque, [3]
+    // kCommToSibling, [4] kCommBusy, [5] kCommRing. Every count is complete
+    // before the work it counts can end, so a worker that leaves after the
+    // launch's termination reads final values (exit record words 37..39)
+    unsigned long long cnt[6];
+};
+// a workgroup's boxes: the workers reach the outboxes from their inbox
+// pointer (wg_boxes), so nothing new rides through run_worker
+template <class Kind, int WPG>
+struct WgBoxes {
+    Inbox<Kind> ib[WPG];
+    Inbox<Kind> out[kOutboxes];
+    CommCtl ctl;
+};
+template <class Kind>
+struct WgBoxes<Kind, 1> {  // a lone worker wave: its (unused) inbox, as ever
+    Inbox<Kind> ib[1];
+};
+template <class Kind, int WPG>
+__device__ __forceinline__ WgBoxes<Kind, WPG> &wg_boxes(Inbox<Kind> *ib) {
+    using Boxes = WgBoxes<Kind, WPG>;
+    static_assert(__builtin_offsetof(Boxes, ib) == 0, "the inboxes lead the workgroup's boxes");
+    return *(WgBoxes<Kind, WPG> *)ib;
+}
+__device__ __forceinline__ void comm_count(CommCtl &c, int i, unsigned long long v) {
+    typedef __attribute__((address_space(3))) unsigned long long lds_u64;
+    if (lane_id() == 0) __hip_atomic_fetch_add((lds_u64 *)&c.cnt[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
 // lane 0's claim of an empty inbox (LDS CAS 0 -> 2; the caller broadcasts it
 // once the reads it issues beside the claim are out)
 template <class Kind>
@@ -1457,7 +1542,7 @@ __device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, W
     const uint32_t lane = (uint32_t)lane_id();
     to_ring = 0;
     const uint32_t cfg = lane0(lds_load(&st.shed_cfg));
-    const uint32_t rule = cfg & 0xffu, max_blocks = (cfg >> 8) & 0xffu;
+    const uint32_t rule = cfg & 0xffu, max_blocks = (cfg >> 8) & 0xffu, comm = (cfg >> 16) & 7u;
     if (rule == 0) return 0;
     const uint32_t fit = (64u * rcp16(mu)) >> 16;  // spawners whose children are one batch (64 / mu)
     uint32_t keep = rule == 2 ? fit : (rule == 3 ? nsp / 4 : nsp / 2);
@@ -1473,6 +1558,10 @@ __device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, W
         sid[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].idle);
         sst[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].state);
     }
+    WgBoxes<Kind, WPG> &bx = wg_boxes<Kind, WPG>(ib);
+    uint32_t ost[kOutboxes];
+#pragma unroll
+    for (int o = 0; o < kOutboxes; ++o) ost[o] = (comm & kCommUseShed) ? lds_load(&bx.out[o].state) : 1u;
     const uint32_t nshed = nsp - keep;  // > 0: nsp > fit >= keep
     uint32_t placed = 0, blocks = 0;
 #pragma unroll
@@ -1495,7 +1584,34 @@ __device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, W
             }
         }
     }
-    to_ring = keep + placed;
+    // what the siblings left over: to the hand-off wave's outboxes, written
+    // exactly as a sibling's block is (the comm wave finds them a taker)
+    uint32_t oplaced = 0;
+    if (comm & kCommUseShed) {
+        uint32_t oblocks = 0;
+#pragma unroll
+        for (int o = 0; o < kOutboxes; ++o) {
+            if (placed + oplaced < nshed && lane0(ost[o]) == 0u) {
+                Inbox<Kind> &to = bx.out[o];
+                const uint32_t left = nshed - placed - oplaced, bs = left < fit ? left : fit, n = bs * mu;
+                const bool valid = lane < n;
+                const uint32_t ok = inbox_claim<Kind>(to);
+                uint32_t w[W];
+                carry_lds_read<TW>(st.cscr, keep + placed + oplaced + (valid ? r_fix : 0u), w);
+                if (lane0(ok)) {
+                    w[W - 2] = ck_fix;
+                    w[W - 1] = ck_fix + 1u;
+                    inbox_fill<Kind>(ctx, to, w, valid, n, g);
+                    oplaced += bs;
+                    ++oblocks;
+                }
+            }
+        }
+        if (oblocks) comm_count(bx.ctl, 1, (unsigned long long)oblocks | (unsigned long long)(oplaced * mu) << 32);
+        if (placed + oplaced < nshed && oblocks < (uint32_t)kOutboxes) comm_count(bx.ctl, 4, 1ull);
+    }
+    to_ring = keep + placed + oplaced;
+    if (comm && to_ring < nsp) comm_count(bx.ctl, 5, 1ull);
     if (lane == 0) {
         st.shed_cnt[kShedExits] += 1u;
         st.shed_cnt[placed == nshed ? kShedPlaced : kShedFallbacks] += 1u;
@@ -1841,6 +1957,136 @@ __device__ __forceinline__ uint32_t push_root(WaveStack<Kind, CAP> &st, uint32_t
     return tout;
 }
 
+// The hand-off wave's loop (see kOutboxes): nap on the outboxes' state words
+// (LDS reads and s_sleep, longer sleeps while every worker is idle), pass
+// each full block on, leave when every worker has left and both outboxes are
+// empty, or on an error. A block in an outbox holds a unit of `outstanding`
+// from its fill, so no worker sees the launch end while one waits here, and
+// a worker leaves only at the end: `left` cannot reach WPG before the last
+// block is served, and a sibling the block is redirected to cannot be
+// closing its inbox (the argument of Inbox, with this wave as the putter).
+// The unit travels with the block: no add here, and `outstanding` is never
+// read. The workers never wait for this wave (a busy outbox sends them to
+// the deques), so its own waits are the enqueue's: the slot wait of
+// enqueue_chunk (1 s, kErrQueueFull) and, with every deque of the slice
+// refusing, cfg.spin_limit on the 100 MHz clock (kErrQueueFull); the nap
+// ends with the workers, whose idle spins are bounded the same way.
+template <class Kind, int CAP, int WPG>
+__device__ void comm_wave(const typename Kind::Ctx &ctx, const PoolView &pool, SchedGlobals *g, const SchedConfig &cfg,
+                          WgBoxes<Kind, WPG> &bx, WaveStack<Kind, CAP> &st_unused) {
+    constexpr int W = Kind::kWords;
+    const uint32_t lane = (uint32_t)lane_id();
+    const uint32_t on = lane0(lds_load(&bx.ctl.on));
+    // the workgroup's home deque: that of its first worker (run_worker)
+    const uint32_t qpx = pool.nq / 8, xcc = xcc_id() & 7u, home_off = ((blockIdx.x * (uint32_t)WPG) / 8u) % qpx;
+    uint32_t occ = 0, naps = 0;
+    PendingChunk pend;  // (never deferred: this wave may wait for its own drain)
+    pend.live = false;
+    while (true) {
+        uint32_t ost[kOutboxes], sid[WPG], sst[WPG];
+#pragma unroll
+        for (int o = 0; o < kOutboxes; ++o) ost[o] = lds_load(&bx.out[o].state);
+        const uint32_t left = lds_load(&bx.ctl.left);
+#pragma unroll
+        for (int a = 0; a < WPG; ++a) {
+            sid[a] = lds_load(&bx.ib[a].idle);
+            sst[a] = lds_load(&bx.ib[a].state);
+        }
+        bool served = false, failed = false;
+#pragma unroll
+        for (int o = 0; o < kOutboxes; ++o) {
+            if (failed || lane0(ost[o]) != 1u) continue;
+            served = true;
+            Inbox<Kind> &blk = bx.out[o];
+            const uint32_t n = lane0(lds_load(&blk.n));
+            bool done = false;
+            if (n > 64u || (n > pool.chunk && !(on & kCommUseRedirect))) {
+                // (never expected: the fillers bound a block by one batch, and by
+                // one chunk wherever it can reach a deque; hx_uts_plan.h)
+                if (lane == 0) dev_error(&g->err, kErrBadTask);
+                failed = true;
+                continue;
+            }
+            if (on & kCommUseRedirect) {
+                // a sibling that has gone idle since the block was filled:
+                // LDS to LDS, the unit travels with the block
+#pragma unroll
+                for (int a = 0; a < WPG; ++a) {
+                    if (done || lane0(sid[a]) != 1u || lane0(sst[a]) != 0u) continue;
+                    if (!lane0(inbox_claim<Kind>(bx.ib[a]))) continue;
+                    comm_count(bx.ctl, 3, 1ull);
+                    if (lane < n) {
+                        const hx_lds_u32 *src = (const hx_lds_u32 *)&blk.w[lane * W];
+                        hx_lds_u32 *dst = (hx_lds_u32 *)&bx.ib[a].w[lane * W];
+#pragma unroll
+                        for (int i = 0; i < W; ++i) dst[i] = src[i];
+                    }
+                    asm volatile("" ::: "memory");
+                    if (lane == 0) {
+                        lds_store(&bx.ib[a].n, n);
+                        lds_store(&bx.ib[a].idle, 0u);
+                        lds_store(&bx.ib[a].state, 1u);  // after the items (DS operations land in order)
+                    }
+                    sst[a] = 1u;
+                    done = true;
+                }
+            }
+            if (!done && n > pool.chunk) {
+                if (lane == 0) dev_error(&g->err, kErrBadTask);
+                failed = true;
+                continue;
+            }
+            if (!done) {
+                // the home deque, then the XCD's others; published at once
+                comm_count(bx.ctl, 2, 1ull);
+                const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
+                for (uint32_t round = 0; !done; ++round) {
+                    for (uint32_t a = 0; a < qpx && !done; ++a)
+                        done = enqueue_chunk<Kind, CAP, true, true>(ctx, pool, g, xcc * qpx + (home_off + a) % qpx, st_unused,
+                                                                    0u, n, occ, pend, false, round != 0, &blk);
+                    if (done) break;
+                    // every deque of the slice refused: their takers drain them
+                    uint32_t e = 0;
+                    if (lane == 0) e = ld_agent(&g->err);
+                    if (lane0(e)) break;
+                    if (__builtin_amdgcn_s_memrealtime() - t0 > 100000ull * cfg.spin_limit) {
+                        if (lane == 0) dev_error(&g->err, kErrQueueFull);
+                        break;
+                    }
+                    __builtin_amdgcn_s_sleep(8);
+                }
+            }
+            if (!done) {
+                failed = true;  // an error: the launch is ending
+                continue;
+            }
+            // the block's words were read before anything above was stored
+            if (lane == 0) lds_store(&blk.state, 0u);
+        }
+        if (failed) break;
+        if (served) {
+            naps = 0;
+            continue;
+        }
+        bool empty = true;
+#pragma unroll
+        for (int o = 0; o < kOutboxes; ++o) empty = empty && lane0(ost[o]) == 0u;
+        if (lane0(left) == (uint32_t)WPG && empty) break;
+        // the error word: one HBM read every 256 naps (a failed launch's
+        // workers leave by themselves; this only ends the wave sooner)
+        if ((++naps & 255u) == 0u) {
+            uint32_t e = 0;
+            if (lane == 0) e = ld_agent(&g->err);
+            if (lane0(e)) break;
+        }
+        bool all_idle = true;
+#pragma unroll
+        for (int a = 0; a < WPG; ++a) all_idle = all_idle && lane0(sid[a]) == 1u;
+        __builtin_amdgcn_s_sleep(1);
+        if (all_idle) __builtin_amdgcn_s_sleep(8);
+    }
+}
+
 // GLOBAL: the launch shares work with the other ranks through g->gview
 // (idle waves take chunks from the global ring, a wave holding spill_lo+
 // items exports a chunk while some rank is idle and none of its own waves
@@ -1898,7 +2144,8 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
             st.shed_g = (unsigned long long)(uintptr_t)g;
             st.shed_ib = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) Inbox<Kind> *)ib;
             st.shed_wave = wave;
-            st.shed_cfg = cfg.narrow_shed;
+            // (bits 16..18 from the workgroup: set only where it has a comm wave)
+            st.shed_cfg = (cfg.narrow_shed & 0xffffu) | lds_load(&wg_boxes<Kind, WPG>(ib).ctl.on) << 16;
         }
         if (lane < kShedCounts) st.shed_cnt[lane] = 0;
     }
@@ -2463,15 +2710,33 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
                     // an idle sibling of this workgroup first (LDS, no HBM
                     // round trip); every sibling's flags read in one go
                     uint32_t sid[WPG], sst[WPG];
+                    WgBoxes<Kind, WPG> &bx = wg_boxes<Kind, WPG>(ib);
+                    uint32_t ost[kOutboxes], comm_on = 0;
 #pragma unroll
                     for (uint32_t a = 1; a < (uint32_t)WPG; ++a) {
                         sid[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].idle);
                         sst[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].state);
                     }
+                    if constexpr (!GLOBAL) {
+                        // (the outboxes' words beside the siblings': one wait)
+                        comm_on = lds_load(&bx.ctl.on);
+#pragma unroll
+                        for (int o = 0; o < kOutboxes; ++o) ost[o] = lds_load(&bx.out[o].state);
+                    }
 #pragma unroll
                     for (uint32_t a = 1; a < (uint32_t)WPG; ++a)
                         if (!ok && lane0(sid[a]) == 1u && lane0(sst[a]) == 0u)
                             ok = inbox_put<Kind, CAP>(ctx, ib[(wave + a) % (uint32_t)WPG], st, bot, n, g);
+                    if constexpr (!GLOBAL) {
+                        // no idle sibling: the hand-off wave's outbox (LDS
+                        // again; it pays the deque's round trips)
+                        if (!ok && (lane0(comm_on) & kCommUseMain)) {
+#pragma unroll
+                            for (int o = 0; o < kOutboxes; ++o)
+                                if (!ok && lane0(ost[o]) == 0u) ok = inbox_put<Kind, CAP>(ctx, bx.out[o], st, bot, n, g);
+                            comm_count(bx.ctl, ok ? 0 : 4, ok ? 1ull | (unsigned long long)n << 32 : 1ull);
+                        }
+                    }
                 }
                 if (!ok) publish_pending<Kind, CAP>(pool, g, pend);  // one deferred chunk at a time
                 // where the chunk goes: the home deque first, then the XCD's others
@@ -2534,6 +2799,11 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
     unsigned long long shed_v = 0;
     if constexpr (kShed) {
         if (lane >= 32 && lane < 32 + kShedCounts) shed_v = st.shed_cnt[lane - 32];
+    }
+    // ... and lanes 37..39 of the workgroup's first two workers its hand-off
+    // counts (final: see CommCtl)
+    if constexpr (WPG > 1 && !GLOBAL) {
+        if (wave < 2 && lane >= 37 && lane < 40) shed_v = wg_boxes<Kind, WPG>(ib).ctl.cnt[3 * wave + (lane - 37)];
     }
     if (active) {
         // only reached on an error break: keep the protocol consistent
@@ -2609,7 +2879,8 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
         }
         if (lane < kWaveCtrWords) g->wave_ctr[(size_t)gid * kWaveCtrWords + lane] = v;
     } else {
-        if (shed_v) add_agent(&g->shed[lane - 32], shed_v);
+        if (shed_v && lane < 32 + kShedCounts) add_agent(&g->shed[lane - 32], shed_v);
+        if (shed_v && lane >= 37) add_agent(&g->comm[3 * wave + (lane - 37)], shed_v);
         if (lane == 0 && n_narrow_in) {
             add_agent(&g->narrow[0], (unsigned long long)n_narrow);
             add_agent(&g->narrow[1], cyc_narrow);

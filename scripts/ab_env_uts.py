@@ -6,8 +6,8 @@ A/B of two builds):
         half=hclib_amd/lib/libhclib_amd.so,HCLIB_HIP_NARROW_SHED=1 ...
 
 Each configuration runs in a process of its own (six launches: the best, all
-six, and the narrow loop's shed counters of the last), ROUNDS times, the
-configurations interleaved."""
+six, and the narrow loop's shed counters and the hand-off waves' counters of
+the last), ROUNDS times, the configurations interleaved."""
 import json
 import os
 import statistics
@@ -30,7 +30,8 @@ for _ in range(6):
     assert r["nodes"] == n
     ms.append(round(r["kernel_ms"], 3))
 c = H.last_shed_counters() if hasattr(H.lib(), "hclib_hip_last_shed_counters") else {}
-print(json.dumps({"ms": ms, "shed": c}))
+cc = H.last_comm_counters() if hasattr(H.lib(), "hclib_hip_last_comm_counters") else {}
+print(json.dumps({"ms": ms, "shed": c, "comm": cc}))
 '''
 res = {}
 for rnd in range(rounds):
@@ -45,6 +46,7 @@ for rnd in range(rounds):
             sys.exit(1)
         d = json.loads(out.stdout.strip().splitlines()[-1])
         res.setdefault(name, []).append(min(d["ms"]))
-        print(tree, rnd, name, "best", min(d["ms"]), "all", d["ms"], "shed", d["shed"], flush=True)
+        print(tree, rnd, name, "best", min(d["ms"]), "all", d["ms"], "shed", d["shed"], "comm", d.get("comm", {}),
+              flush=True)
 for name, v in res.items():
     print(f"{tree} {name}: median of bests {statistics.median(v):.3f} min {min(v):.3f} max {max(v):.3f} ms {v}")
