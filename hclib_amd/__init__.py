@@ -162,6 +162,14 @@ class BfsResult(C.Structure):
                 ("kernel_ms", C.c_double), ("busy_frac", C.c_double)]
 
 
+class CfdResult(C.Structure):
+    """hclib_hip_cfd_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("puts", C.c_uint64), ("releases", C.c_uint64), ("stages", C.c_uint64),
+                ("bytes_moved", C.c_uint64), ("block", C.c_int), ("form", C.c_int),
+                ("kernel_ms", C.c_double), ("elements_per_s", C.c_double)]
+
+
 class HealthParams(C.Structure):
     """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
 
@@ -272,6 +280,7 @@ EXPORTS_HIP = [
     "hclib_hip_fft", "hclib_hip_fft_factors", "hclib_hip_fft_twiddles", "hclib_hip_fft_bounds", "hclib_hip_fft_last_ticks",
     "hclib_hip_jacobi", "hclib_hip_jacobi_rhs", "hclib_hip_jacobi_bounds",
     "hclib_hip_bfs", "hclib_hip_bfs_bounds", "hclib_hip_bfs_read_input",
+    "hclib_hip_cfd", "hclib_hip_cfd_bounds", "hclib_hip_cfd_read_input",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -392,6 +401,10 @@ def lib():
         L.hclib_hip_bfs_bounds.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int,
                                            C.POINTER(C.c_uint64)]
         L.hclib_hip_bfs_read_input.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.hclib_hip_cfd.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int,
+                                    C.c_void_p, C.POINTER(CfdResult)]
+        L.hclib_hip_cfd_bounds.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.hclib_hip_cfd_read_input.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
         _lib = L
     return _lib
 
@@ -1217,6 +1230,78 @@ def bfs_bounds(graph_or_path, form: str = "level") -> dict:
     _check(lib().hclib_hip_bfs_bounds(st.ctypes.data, dg.ctypes.data, st.size, ed.ctypes.data if ed.size else None,
                                       ed.size, src, _bfs_form(form), out), "hclib_hip_bfs_bounds")
     return {"arena_bytes": out[0], "items": out[1]}
+
+
+# -------------------------------------------------------------- Rodinia CFD
+CFD_FORMS = {"dag": 0, "phases": 1}  # HCLIB_HIP_CFD_DAG / _PHASES
+
+
+def cfd_read_input(path) -> dict:
+    """A Rodinia CFD mesh file through hclib_hip_cfd_read_input (the reference's
+    reader, euler3d_cpu_double.ref.cpp:417-455), on the host alone: {"nel",
+    "nelr", "areas" [nelr], "neighbours" [nelr, 4] (int32: an element, -1 wing,
+    -2 far field), "normals" [nelr, 4, 3] (negated)}, the rows from nel on
+    copies of row nel - 1, as cfd() takes it."""
+    import numpy as np
+
+    counts = (C.c_int64 * 2)()
+    _check(lib().hclib_hip_cfd_read_input(os.fsencode(path), None, None, None, counts), "hclib_hip_cfd_read_input")
+    nelr = int(counts[1])
+    m = {"nel": int(counts[0]), "nelr": nelr, "areas": np.empty(nelr, dtype=np.float64),
+         "neighbours": np.empty((nelr, 4), dtype=np.int32), "normals": np.empty((nelr, 4, 3), dtype=np.float64)}
+    _check(lib().hclib_hip_cfd_read_input(os.fsencode(path), m["areas"].ctypes.data, m["neighbours"].ctypes.data,
+                                          m["normals"].ctypes.data, counts), "hclib_hip_cfd_read_input")
+    return m
+
+
+def _cfd_mesh(path_or_arrays):
+    import numpy as np
+
+    m = cfd_read_input(path_or_arrays) if isinstance(path_or_arrays, (str, bytes, os.PathLike)) else path_or_arrays
+    nel = int(m["nel"])
+    nelr = 8 * ((nel + 7) // 8) if nel >= 1 else 0
+    ar = np.ascontiguousarray(m["areas"], dtype=np.float64).ravel()
+    nb = np.ascontiguousarray(m["neighbours"], dtype=np.int32).ravel()
+    nr = np.ascontiguousarray(m["normals"], dtype=np.float64).ravel()
+    if nel >= 1 and (ar.size != nelr or nb.size != nelr * 4 or nr.size != nelr * 12):
+        raise ValueError(f"cfd: areas, neighbours and normals must hold nelr = {nelr} rows (1, 4 and 4 x 3 entries each)")
+    return nel, nelr, ar, nb, nr
+
+
+def cfd(path_or_arrays, iterations: int = 5, block: int = 0, form: str = "dag", variables0=None):
+    """Rodinia CFD on the device promise DAG (hclib_hip_cfd): `iterations`
+    iterations of the three-stage Euler solver over the mesh path_or_arrays (a
+    file of Rodinia's format, or what cfd_read_input returns); returns
+    (variables [nelr, 5] float64, the reference's bits, stats). variables0: the
+    initial state, default the far field everywhere. block: elements per task
+    (a multiple of 8 in [8, 1024], 0 = the default); form "dag" is one launch
+    whose tasks await only the blocks the mesh connects them to, "phases" one
+    kernel per stage, the reference's schedule; results depend on neither."""
+    import numpy as np
+
+    if form not in CFD_FORMS:
+        raise ValueError(f"cfd: form {form!r} is not one of {sorted(CFD_FORMS)}")
+    nel, nelr, ar, nb, nr = _cfd_mesh(path_or_arrays)
+    v0 = None
+    if variables0 is not None:
+        v0 = np.ascontiguousarray(variables0, dtype=np.float64).ravel()
+        if v0.size != nelr * 5:
+            raise ValueError(f"cfd: variables0 must hold nelr x 5 = {nelr * 5} values")
+    out = np.empty((nelr, 5), dtype=np.float64)
+    r = CfdResult()
+    _check(lib().hclib_hip_cfd(nel, ar.ctypes.data, nb.ctypes.data, nr.ctypes.data, None if v0 is None else v0.ctypes.data,
+                               iterations, block, CFD_FORMS[form], out.ctypes.data, C.byref(r)), "hclib_hip_cfd")
+    return out, {k: getattr(r, k) for k, _ in CfdResult._fields_}
+
+
+def cfd_bounds(path_or_arrays, iterations: int = 5, block: int = 0) -> dict:
+    """What a cfd() launch creates (hclib_hip_cfd_bounds), exact and on the host
+    alone: tasks, awaits, stages, the longest waiter list, the bytes of device
+    memory and the bytes the tasks move. Raises as the launch would."""
+    nel, nelr, ar, nb, nr = _cfd_mesh(path_or_arrays)
+    out = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_cfd_bounds(nel, nb.ctypes.data, iterations, block, out), "hclib_hip_cfd_bounds")
+    return dict(zip(("tasks", "awaits", "stages", "max_waiters", "arena_bytes", "bytes_moved"), out))
 
 
 # --------------------------------------------------------------- BOTS Health

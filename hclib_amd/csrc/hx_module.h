@@ -35,6 +35,7 @@ enum ArenaId {
     kArenaAlignment,   // class counters, matrix, sequence and pair tables, pair records, codes, row slices
     kArenaFft,         // class counters, the two ping-pong buffers and the twiddle table
     kArenaJacobi,      // f and the two ping-pong grids
+    kArenaCfd,         // the mesh, the two ping-pong states, old and the step factors
     kArenaUtsTables,  // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };

@@ -89,6 +89,13 @@
  *                                    139-182), as frontier items of the
  *                                    work-stealing megakernel whose last finisher
  *                                    opens the next level
+ *   hclib_hip_cfd                    the 41 hclib_forasync_future sweeps of Rodinia
+ *                                    cfd and the hclib_future_wait after each
+ *                                    (rodinia/cfd/euler3d_cpu_double.cpp:74-79,
+ *                                    147-152, 228-233, 294-299, 460-465; the loop
+ *                                    euler3d_cpu_double.ref.cpp:470-482), as awaits
+ *                                    between (stage, block) tasks read off the
+ *                                    mesh, in one launch of the device promise DAG
  *   hclib_hip_atomic_*,            the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -1241,6 +1248,60 @@ int hclib_hip_bfs(const int32_t *starting, const int32_t *degree, int n_nodes, c
 int hclib_hip_bfs_bounds(const int32_t *starting, const int32_t *degree, int n_nodes, const int32_t *edges,
                          int n_edges, int source, int form, uint64_t out[2]);
 int hclib_hip_bfs_read_input(const char *path, int32_t *starting, int32_t *degree, int32_t *edges, int64_t counts[3]);
+
+/* Rodinia CFD (test/performance-regression/full-apps/rodinia/cfd/
+ * euler3d_cpu_double.cpp; the arithmetic as euler3d_cpu_double.ref.cpp states
+ * it): `iterations` iterations of the three-stage Runge-Kutta Euler solver over
+ * an unstructured mesh, as ONE launch of the device promise DAG, bit-identical
+ * to the reference built without fused multiply-add.
+ * The mesh is what the reference holds after reading (:417-455): nelr = 8 *
+ * ceil(nel / 8) rows, the rows from nel on copies of row nel - 1; areas[nelr];
+ * neighbours[nelr * 4], an element index >= 0, -1 a wing face, -2 a far-field
+ * face (any other negative: a face without a flux, as the reference's chain of
+ * ifs leaves it); normals[nelr * 4 * 3], already negated.
+ * variables0: nelr * 5 doubles (density, momentum x y z, density energy per
+ * element), or NULL for the far field everywhere (:127-130, :383-408).
+ * variables: nelr * 5 doubles, the state after the last iteration (dump()
+ * prints its first nel rows). iterations == 0 launches nothing and copies the
+ * initial state.
+ * block: elements per task, a multiple of 8 in [8, 1024], 0 = 256. The result
+ * does not depend on it.
+ *   HCLIB_HIP_CFD_DAG     one task per (stage, block), stage = 3 iteration + j;
+ *       a task awaits, of the stage before, the blocks its elements' faces
+ *       name, the blocks that name it, and itself (hclib_amd/csrc/
+ *       hx_cfd_plan.h has why this orders the two state buffers' overwrites).
+ *   HCLIB_HIP_CFD_PHASES  the same element body as one plain kernel per stage,
+ *       stream-ordered: the reference's join per sweep, for comparison.
+ * result: tasks, puts, releases from the DAG launch (phases: tasks = the
+ * workgroups run, no puts); stages = 3 iterations; bytes_moved = the plan's
+ * traffic model; kernel_ms; elements_per_s = nelr * stages over kernel time.
+ * EINVAL, before the device is touched, where the reference reads outside its
+ * arrays: a NULL array, nel < 1 (or so large that the reference's int indices
+ * overflow), iterations < 0, an unknown form, a block outside its limits, a
+ * neighbour index >= nelr (one in [nel, nelr) names a padded copy and is
+ * accepted), 3 * iterations * nblocks >= 2^26 tasks or 2^32 awaits.
+ * hclib_hip_cfd_bounds: host only, with the same checks, exact: out[0] tasks,
+ * [1] awaits, [2] stages, [3] the longest waiter list of a promise, [4] the
+ * bytes of device memory, [5] bytes_moved.
+ * hclib_hip_cfd_read_input: host only: the reference's reader. With every
+ * array NULL it only sizes: counts[0] = nel, counts[1] = nelr. Otherwise the
+ * arrays hold nelr rows and counts[0] is the nel a first call reported. EINVAL
+ * for a file that cannot be opened, is truncated or holds a token that is no
+ * number, and for nel < 1. */
+typedef struct {
+    uint64_t tasks, puts, releases;   /* from the DAG launch */
+    uint64_t stages, bytes_moved;     /* the plan's */
+    int block, form;                  /* as run */
+    double kernel_ms;                 /* device events around the launch (phases: around all stages) */
+    double elements_per_s;            /* nelr * stages over kernel time */
+} hclib_hip_cfd_result_t;
+#define HCLIB_HIP_CFD_DAG 0
+#define HCLIB_HIP_CFD_PHASES 1
+int hclib_hip_cfd(int nel, const double *areas, const int *neighbours, const double *normals,
+                  const double *variables0 /* NULL: far field */, int iterations, int block, int form,
+                  double *variables /* nelr * 5 */, hclib_hip_cfd_result_t *result);
+int hclib_hip_cfd_read_input(const char *path, double *areas, int *neighbours, double *normals, int64_t counts[2]);
+int hclib_hip_cfd_bounds(int nel, const int *neighbours, int iterations, int block, uint64_t out[6]);
 
 #ifdef __cplusplus
 }
