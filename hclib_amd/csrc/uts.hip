@@ -357,8 +357,8 @@ __global__ __launch_bounds__(64 * uts_block_waves(WPG, GLOBAL)) void k_uts_searc
     constexpr bool kComm = uts_block_waves(WPG, GLOBAL) > WPG;
     using K = UtsKind<MODE, FEAT, CAP>;
     __shared__ WaveStack<K, kUtsCap> st[WPG];
-    __shared__ WgBoxes<K, WPG> bx;
-    static_assert(sizeof(st) + sizeof(bx) + (MODE == kUtsBin ? 0 : sizeof(s_rules) + sizeof(s_thr)) <= 160 * 1024,
+    WgBoxes<K, WPG> &bx = wg_static_boxes<K, WPG>();  // the workgroup's one static LDS object
+    static_assert(sizeof(st) + sizeof(WgBoxes<K, WPG>) + (MODE == kUtsBin ? 0 : sizeof(s_rules) + sizeof(s_thr)) <= 160 * 1024,
                   "a workgroup's rings, boxes and rule tables fit a CU's LDS");
     Inbox<K> *ib = bx.ib;
     const uint32_t wave = WPG > 1 ? threadIdx.x / 64 : 0;

@@ -423,15 +423,18 @@ constexpr uint32_t kMaxChildren = 1u << 24;  // kend shares its descriptor word 
 // what the narrow loop's overflow exit (narrow_shed) needs of its
 // surroundings, parked in LDS (run_worker stores it once) so that none of it
 // rides along the loop's levels in registers, and that exit's counts
-// (kShed*); on the rings that have the carry slots (WaveStack::kCarryLds)
+// (kShed*); on the rings that have the carry slots (WaveStack::kCarryLds).
+// The first 16 bytes lead the (16-byte aligned) WaveStack: the exit reads
+// them as one ds_read_b128. The workgroup's boxes need no word here: they
+// are one static LDS object (wg_static_boxes)
 template <bool ON>
 struct ShedSlots {};
 template <>
 struct ShedSlots<true> {
     unsigned long long shed_g;  // SchedGlobals *
-    uint32_t shed_ib;           // LDS address of the workgroup's inboxes
-    uint32_t shed_wave;         // this wave's index among them
+    uint32_t shed_wave;         // this wave's index among the workgroup's inboxes
     uint32_t shed_cfg;          // SchedConfig::narrow_shed
+    uint32_t shed_pad;
     uint32_t shed_cnt[kShedCounts];
 };
 
@@ -1415,8 +1418,13 @@ __device__ __forceinline__ NarrowState<Kind::kTmplWords> narrow_loop(
 // the chunk becomes visible, and the taker inherits it, so no wave can see
 // 0 while a chunk waits in an inbox. A wave that leaves the megakernel closes
 // its inbox (state 3) so nothing is put there afterwards.
+typedef __attribute__((address_space(3))) hx_u32x4 hx_lds_u32x4;
+typedef uint32_t hx_u32x2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) hx_u32x2 hx_lds_u32x2;
+// (16-byte aligned, the items behind a 16-byte head: an 8-word item goes out
+// and comes in as two 16-byte DS operations; {state, n} are one 8-byte read)
 template <class Kind>
-struct Inbox {
+struct alignas(16) Inbox {
     uint32_t state;  // 0 empty, 2 being filled, 1 full, 3 closed (owner left)
     uint32_t n;
     uint32_t idle;   // the owner wave holds no work
@@ -1466,6 +1474,15 @@ __device__ __forceinline__ WgBoxes<Kind, WPG> &wg_boxes(Inbox<Kind> *ib) {
     static_assert(__builtin_offsetof(Boxes, ib) == 0, "the inboxes lead the workgroup's boxes");
     return *(WgBoxes<Kind, WPG> *)ib;
 }
+// The boxes of a workgroup of WPG > 1 waves are one static LDS object: the
+// kernel declares none of its own, and the address of every box's flags is a
+// constant of the kernel, so the narrow loop's overflow exit reads them all
+// without first loading where they are.
+template <class Kind, int WPG>
+__device__ __forceinline__ WgBoxes<Kind, WPG> &wg_static_boxes() {
+    __shared__ WgBoxes<Kind, WPG> bx;
+    return bx;
+}
 __device__ __forceinline__ void comm_count(CommCtl &c, int i, unsigned long long v) {
     typedef __attribute__((address_space(3))) unsigned long long lds_u64;
     if (lane_id() == 0) __hip_atomic_fetch_add((lds_u64 *)&c.cnt[i], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -1491,13 +1508,24 @@ __device__ __forceinline__ void inbox_fill(const typename Kind::Ctx &ctx, Inbox<
     kind_trace_item<Kind>(ctx, w, valid, 2u, true);
     if (valid) {
         // (address-space-3 stores: DS operations, in order with the flags' below)
-        hx_lds_u32 *dst = (hx_lds_u32 *)&ib.w[(uint32_t)lane_id() * W];
+        if constexpr (W == 8) {
+            // a 32-byte item at a 16-byte aligned offset: two ds_write_b128
+            hx_lds_u32x4 *dst = (hx_lds_u32x4 *)&ib.w[(uint32_t)lane_id() * W];
+            dst[0] = hx_u32x4{w[0], w[1], w[2], w[3]};
+            dst[1] = hx_u32x4{w[4], w[5], w[6], w[7]};
+        } else {
+            hx_lds_u32 *dst = (hx_lds_u32 *)&ib.w[(uint32_t)lane_id() * W];
 #pragma unroll
-        for (int i = 0; i < W; ++i) dst[i] = w[i];
+            for (int i = 0; i < W; ++i) dst[i] = w[i];
+        }
     }
     asm volatile("" ::: "memory");
     if (lane_id() == 0) {
-        add_agent(&g->outstanding, 1u);  // the chunk's unit, before it becomes visible
+        // the chunk's unit, before it becomes visible: a global_ atomic (through
+        // the generic pointer it is a FLAT one, which counts on lgkmcnt too and
+        // so stands in every later wait for LDS)
+        typedef __attribute__((address_space(1))) uint32_t glb_u32;
+        __hip_atomic_fetch_add((glb_u32 *)&g->outstanding, 1u, __ATOMIC_RELAXED, HX_AGENT);
         lds_store(&ib.n, n);
         lds_store(&ib.idle, 0u);
         lds_store(&ib.state, 1u);  // after the items (one wave's DS operations land in order)
@@ -1533,105 +1561,139 @@ __device__ bool inbox_put(const typename Kind::Ctx &ctx, Inbox<Kind> &ib, WaveSt
 // straight into the inboxes of idle siblings: no ring traffic and no return
 // to the main loop between two levels of the chain. Returns keep (0: shedding
 // is off) and in `to_ring` the first spawner rank it could not place (nsp:
-// none left). Every sibling's flags are read in one go, as run_worker's
-// give-away does.
+// none left).
+// Two LDS round trips to the first block's items. The first brings all the
+// exit must know: the parked record (one 16-byte read) and, lane b reading
+// box b of the workgroup's static boxes, every inbox's and outbox's flags
+// (one 16-byte read per lane), which a ballot turns into the mask of free
+// boxes; the rule, the blocks and the candidates (siblings from this wave's
+// right-hand neighbour on, then the outboxes) are scalar work behind that one
+// wait. The second is a block's claim with the read of its carry slots issued
+// ahead of it; a lost claim (rare) goes on to the next candidate. The counts
+// are adds without a return value: nothing waits on the way back into the loop.
 template <class Kind, int CAP, int WPG>
 __device__ __forceinline__ uint32_t narrow_shed(const typename Kind::Ctx &ctx, WaveStack<Kind, CAP> &st, uint32_t mu,
                                                 uint32_t nsp, uint32_t r_fix, uint32_t ck_fix, uint32_t &to_ring) {
     constexpr int TW = Kind::kTmplWords, W = Kind::kWords;
-    const uint32_t lane = (uint32_t)lane_id();
+    using Boxes = WgBoxes<Kind, WPG>;
+    constexpr uint32_t kBoxes = (uint32_t)WPG + (uint32_t)kOutboxes, kBoxBytes = (uint32_t)sizeof(Inbox<Kind>);
+    constexpr uint32_t kSibs = (1u << (WPG - 1)) - 1u;  // the candidate mask's sibling bits
+    static_assert(__builtin_offsetof(Boxes, out) == WPG * sizeof(Inbox<Kind>), "box WPG + o is outbox o");
+    static_assert((WPG & (WPG - 1)) == 0, "sibling indices wrap with a mask");
+    static_assert(__builtin_offsetof(ShedSlots<true>, shed_g) == 0 && __builtin_offsetof(ShedSlots<true>, shed_cfg) == 12,
+                  "the parked record is the stack's first 16 bytes");
     to_ring = 0;
-    const uint32_t cfg = lane0(lds_load(&st.shed_cfg));
+    // the exit's own copies of the lane index and of the boxes' (constant) LDS
+    // address: what is computed from them is computed here, not hoisted into
+    // registers that would then live through every level of the loop
+    uint32_t lane = (uint32_t)lane_id();
+    typedef __attribute__((address_space(3))) Boxes lds_boxes;
+    uint32_t bxa = (uint32_t)(uintptr_t)(lds_boxes *)&wg_static_boxes<Kind, WPG>();
+    asm volatile("" : "+v"(lane), "+s"(bxa));
+    Boxes &bx = *(Boxes *)(lds_boxes *)(uintptr_t)bxa;
+    char *const box0 = (char *)&bx;
+    asm volatile("" ::: "memory");
+    const hx_u32x4 rec = *(const hx_lds_u32x4 *)&st.shed_g;  // {g, wave, cfg}
+    const hx_lds_u32 *flp = (const hx_lds_u32 *)(box0 + (lane < kBoxes ? lane : 0u) * kBoxBytes);
+    const uint32_t fst = flp[0], fid = flp[2];  // state and idle: one ds_read2_b32
+    asm volatile("" ::: "memory");
+    // free: an inbox empty with its owner idle, an outbox empty
+    const unsigned long long fm =
+        __builtin_amdgcn_ballot_w64(lane < kBoxes && fst == 0u && (fid == 1u || lane >= (uint32_t)WPG));
+    const uint32_t cfg = lane0(rec.w), wave = lane0(rec.z);
     const uint32_t rule = cfg & 0xffu, max_blocks = (cfg >> 8) & 0xffu, comm = (cfg >> 16) & 7u;
     if (rule == 0) return 0;
     const uint32_t fit = (64u * rcp16(mu)) >> 16;  // spawners whose children are one batch (64 / mu)
-    uint32_t keep = rule == 2 ? fit : (rule == 3 ? nsp / 4 : nsp / 2);
+    // (selects, no branches: the exit's instructions are the chain's time)
+    uint32_t keep = nsp >> (rule == 3 ? 2 : 1);
+    keep = rule == 2 ? fit : keep;
     keep = keep > fit ? fit : (keep == 0 ? 1u : keep);
-    const uint32_t wave = lane0(lds_load(&st.shed_wave));
-    typedef __attribute__((address_space(3))) Inbox<Kind> lds_inbox;
-    Inbox<Kind> *ib = (Inbox<Kind> *)(lds_inbox *)(uintptr_t)lane0(lds_load(&st.shed_ib));
-    const unsigned long long gp = st.shed_g;
-    SchedGlobals *g = (SchedGlobals *)(((unsigned long long)lane0((uint32_t)(gp >> 32)) << 32) | lane0((uint32_t)gp));
-    uint32_t sid[WPG], sst[WPG];
-#pragma unroll
-    for (uint32_t a = 1; a < (uint32_t)WPG; ++a) {
-        sid[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].idle);
-        sst[a] = lds_load(&ib[(wave + a) % (uint32_t)WPG].state);
-    }
-    WgBoxes<Kind, WPG> &bx = wg_boxes<Kind, WPG>(ib);
-    uint32_t ost[kOutboxes];
-#pragma unroll
-    for (int o = 0; o < kOutboxes; ++o) ost[o] = (comm & kCommUseShed) ? lds_load(&bx.out[o].state) : 1u;
+    SchedGlobals *g = (SchedGlobals *)(((unsigned long long)lane0(rec.y) << 32) | lane0(rec.x));
+    // candidates in order: bit a - 1 the sibling (wave + a) % WPG, bit WPG - 1 + o outbox o
+    const uint32_t ibm = (uint32_t)fm & ((1u << WPG) - 1u);
+    uint32_t cand = (((ibm | ibm << WPG) >> wave) >> 1) & kSibs;
+    if (max_blocks == 0) cand = 0;
+    if (comm & kCommUseShed) cand |= ((uint32_t)fm >> WPG & ((1u << kOutboxes) - 1u)) << (WPG - 1);
     const uint32_t nshed = nsp - keep;  // > 0: nsp > fit >= keep
-    uint32_t placed = 0, blocks = 0;
-#pragma unroll
-    for (uint32_t a = 1; a < (uint32_t)WPG; ++a) {
-        if (placed < nshed && blocks < max_blocks && lane0(sid[a]) == 1u && lane0(sst[a]) == 0u) {
-            Inbox<Kind> &to = ib[(wave + a) % (uint32_t)WPG];
-            const uint32_t bs = nshed - placed < fit ? nshed - placed : fit, n = bs * mu;
-            const bool valid = lane < n;
-            // item o of the block is child o % mu of spawner keep + placed + o / mu
-            // (its slot's read goes out beside the claim)
-            const uint32_t ok = inbox_claim<Kind>(to);
-            uint32_t w[W];
-            carry_lds_read<TW>(st.cscr, keep + placed + (valid ? r_fix : 0u), w);
-            if (lane0(ok)) {
-                w[W - 2] = ck_fix;
-                w[W - 1] = ck_fix + 1u;
-                inbox_fill<Kind>(ctx, to, w, valid, n, g);
+    uint32_t placed = 0, blocks = 0, oplaced = 0, oblocks = 0;
+    while (cand != 0 && placed + oplaced < nshed) {
+        const uint32_t j = (uint32_t)__builtin_ctz(cand);
+        cand &= cand - 1u;
+        const bool sib = j < (uint32_t)(WPG - 1);
+        const uint32_t box = sib ? (wave + 1u + j) & (uint32_t)(WPG - 1) : j + 1u;
+        Inbox<Kind> &to = *(Inbox<Kind> *)(box0 + box * kBoxBytes);
+        const uint32_t done = placed + oplaced, left = nshed - done, bs = left < fit ? left : fit, n = bs * mu;
+        const bool valid = lane < n;
+        // item o of the block is child o % mu of spawner keep + done + o / mu: its
+        // slot's read is issued ahead of the claim (whose compiler barrier it cannot
+        // sink below) and lands with it; it is unused when the claim is lost
+        uint32_t w[W];
+        carry_lds_read<TW>(st.cscr, keep + done + (valid ? r_fix : 0u), w);
+        const uint32_t ok = inbox_claim<Kind>(to);
+        // one wait for the claim and the slots, stated where every lane passes: the
+        // claim's own wait stands inside lane 0's branch, and the compiler would
+        // otherwise hold the slots' registers pending on the path around it and
+        // wait for the item stores before it next writes one of them
+        __builtin_amdgcn_s_waitcnt(0xC07F);  // lgkmcnt(0)
+        if (lane0(ok)) {
+            w[W - 2] = ck_fix;
+            w[W - 1] = ck_fix + 1u;
+            inbox_fill<Kind>(ctx, to, w, valid, n, g);
+            if (sib) {
                 placed += bs;
-                ++blocks;
+                if (++blocks >= max_blocks) cand &= ~kSibs;
+            } else {
+                // (an outbox, written exactly as a sibling's block is: the comm wave
+                // finds it a taker)
+                oplaced += bs;
+                ++oblocks;
             }
         }
-    }
-    // what the siblings left over: to the hand-off wave's outboxes, written
-    // exactly as a sibling's block is (the comm wave finds them a taker)
-    uint32_t oplaced = 0;
-    if (comm & kCommUseShed) {
-        uint32_t oblocks = 0;
-#pragma unroll
-        for (int o = 0; o < kOutboxes; ++o) {
-            if (placed + oplaced < nshed && lane0(ost[o]) == 0u) {
-                Inbox<Kind> &to = bx.out[o];
-                const uint32_t left = nshed - placed - oplaced, bs = left < fit ? left : fit, n = bs * mu;
-                const bool valid = lane < n;
-                const uint32_t ok = inbox_claim<Kind>(to);
-                uint32_t w[W];
-                carry_lds_read<TW>(st.cscr, keep + placed + oplaced + (valid ? r_fix : 0u), w);
-                if (lane0(ok)) {
-                    w[W - 2] = ck_fix;
-                    w[W - 1] = ck_fix + 1u;
-                    inbox_fill<Kind>(ctx, to, w, valid, n, g);
-                    oplaced += bs;
-                    ++oblocks;
-                }
-            }
-        }
-        if (oblocks) comm_count(bx.ctl, 1, (unsigned long long)oblocks | (unsigned long long)(oplaced * mu) << 32);
-        if (placed + oplaced < nshed && oblocks < (uint32_t)kOutboxes) comm_count(bx.ctl, 4, 1ull);
     }
     to_ring = keep + placed + oplaced;
-    if (comm && to_ring < nsp) comm_count(bx.ctl, 5, 1ull);
-    if (lane == 0) {
-        st.shed_cnt[kShedExits] += 1u;
-        st.shed_cnt[placed == nshed ? kShedPlaced : kShedFallbacks] += 1u;
-        st.shed_cnt[kShedBlocks] += blocks;
-        st.shed_cnt[kShedItems] += placed * mu;
+    // the hand-off counts, behind one test: an exit placed whole with siblings has none
+    if (comm != 0 && (oblocks | (nsp - to_ring)) != 0) {
+        if (comm & kCommUseShed) {
+            if (oblocks) comm_count(bx.ctl, 1, (unsigned long long)oblocks | (unsigned long long)(oplaced * mu) << 32);
+            if (to_ring < nsp && oblocks < (uint32_t)kOutboxes) comm_count(bx.ctl, 4, 1ull);
+        }
+        if (to_ring < nsp) comm_count(bx.ctl, 5, 1ull);
+    }
+    {
+        // lane i adds count i: one DS add that returns nothing, so nothing waits on
+        // the way back into the loop (the values first, then plain selects)
+        const uint32_t full = placed == nshed ? 1u : 0u, items = placed * mu;
+        uint32_t v = 1u - full;  // kShedFallbacks
+        v = lane == (uint32_t)kShedExits ? 1u : v;
+        v = lane == (uint32_t)kShedPlaced ? full : v;
+        v = lane == (uint32_t)kShedBlocks ? blocks : v;
+        v = lane == (uint32_t)kShedItems ? items : v;
+        if (lane < (uint32_t)kShedCounts)
+            __hip_atomic_fetch_add((hx_lds_u32 *)&st.shed_cnt[lane], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
     return keep;
 }
 
-// take a full inbox into the (empty) ring; returns the items (0: empty)
+// take a full inbox into the (empty) ring; returns the items (0: empty). One
+// LDS round trip on a hit: {state, n} are one 8-byte read and every lane's
+// item is read behind it in the same wait (the LDS performs a wave's reads in
+// issue order: an item read issued after a state read that saw "full" sees
+// the items, which the giver wrote before the state)
 template <class Kind, int CAP>
 __device__ uint32_t inbox_take(const typename Kind::Ctx &ctx, Inbox<Kind> &ib, WaveStack<Kind, CAP> &st) {
     constexpr int W = Kind::kWords;
+    static_assert(W == 8, "an inbox item is two 16-byte reads");
     const int lane = lane_id();
-    if (lane0(lds_load(&ib.state)) != 1u) return 0;
-    const uint32_t n = lane0(lds_load(&ib.n));
+    asm volatile("" ::: "memory");
+    const hx_u32x2 hd = *(const hx_lds_u32x2 *)&ib.state;  // {state, n}
+    asm volatile("" ::: "memory");  // the state's read is issued first
+    const hx_lds_u32x4 *src = (const hx_lds_u32x4 *)&ib.w[(uint32_t)lane * W];
+    const hx_u32x4 a = src[0], b = src[1];
+    asm volatile("" ::: "memory");
+    if (lane0(hd.x) != 1u) return 0;
+    const uint32_t n = lane0(hd.y);
     if ((uint32_t)lane < n) {
-        uint32_t w[W];
-#pragma unroll
-        for (int i = 0; i < W; ++i) w[i] = ib.w[(uint32_t)lane * W + i];
+        uint32_t w[W] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
         store_tmpl<Kind, CAP>(st, (uint32_t)lane, w);
         st.d[lane] = make_uint2(w[W - 2], w[W - 1]);
         kind_trace_item<Kind>(ctx, w, true, 3u, true);
@@ -2142,7 +2204,6 @@ __device__ void run_worker(const typename Kind::Ctx &ctx, const PoolView &pool, 
     if constexpr (kShed) {
         if (lane == 0) {
             st.shed_g = (unsigned long long)(uintptr_t)g;
-            st.shed_ib = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) Inbox<Kind> *)ib;
             st.shed_wave = wave;
             // (bits 16..18 from the workgroup: set only where it has a comm wave)
             st.shed_cfg = (cfg.narrow_shed & 0xffffu) | lds_load(&wg_boxes<Kind, WPG>(ib).ctl.on) << 16;
