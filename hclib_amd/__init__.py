@@ -170,6 +170,14 @@ class CfdResult(C.Structure):
                 ("kernel_ms", C.c_double), ("elements_per_s", C.c_double)]
 
 
+class SradResult(C.Structure):
+    """hclib_hip_srad_result_t."""
+
+    _fields_ = [("tasks", C.c_uint64), ("puts", C.c_uint64), ("releases", C.c_uint64), ("awaits", C.c_uint64),
+                ("iterations", C.c_uint64), ("bytes_moved", C.c_uint64), ("block", C.c_int), ("form", C.c_int),
+                ("kernel_ms", C.c_double)]
+
+
 class HealthParams(C.Structure):
     """hclib_hip_health_params_t: the ten settings of a BOTS health input file."""
 
@@ -281,6 +289,7 @@ EXPORTS_HIP = [
     "hclib_hip_jacobi", "hclib_hip_jacobi_rhs", "hclib_hip_jacobi_bounds",
     "hclib_hip_bfs", "hclib_hip_bfs_bounds", "hclib_hip_bfs_read_input",
     "hclib_hip_cfd", "hclib_hip_cfd_bounds", "hclib_hip_cfd_read_input",
+    "hclib_hip_srad", "hclib_hip_srad_image", "hclib_hip_srad_bounds",
     "hclib_atomic_create", "hclib_atomic_init", "hclib_atomic_update", "hclib_atomic_gather",
 ]
 
@@ -405,6 +414,10 @@ def lib():
                                     C.c_void_p, C.POINTER(CfdResult)]
         L.hclib_hip_cfd_bounds.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         L.hclib_hip_cfd_read_input.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int64)]
+        L.hclib_hip_srad.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int,
+                                     C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.POINTER(SradResult)]
+        L.hclib_hip_srad_image.argtypes = [C.c_int, C.c_int, C.c_void_p]
+        L.hclib_hip_srad_bounds.argtypes = [C.c_int] * 8 + [C.POINTER(C.c_uint64)]
         _lib = L
     return _lib
 
@@ -1302,6 +1315,64 @@ def cfd_bounds(path_or_arrays, iterations: int = 5, block: int = 0) -> dict:
     out = (C.c_uint64 * 6)()
     _check(lib().hclib_hip_cfd_bounds(nel, nb.ctypes.data, iterations, block, out), "hclib_hip_cfd_bounds")
     return dict(zip(("tasks", "awaits", "stages", "max_waiters", "arena_bytes", "bytes_moved"), out))
+
+
+# ------------------------------------------------------------- Rodinia SRAD
+SRAD_FORMS = {"dag": 0, "phases": 1}  # HCLIB_HIP_SRAD_DAG / _PHASES
+
+
+def srad(j0, roi, lam: float = 0.5, niter: int = 2, block: int = 0, form: str = "dag"):
+    """Rodinia SRAD on the device promise DAG (hclib_hip_srad): `niter`
+    iterations of speckle-reducing anisotropic diffusion over the float32 image
+    `j0` (what srad_image returns, or any positive image whose sides are
+    multiples of 16). roi = (r1, r2, c1, c2), rows and columns of the region of
+    interest, both ends included. Returns (J, stats); stats["q0sqr"] holds each
+    iteration's scalar of the serial section, read back from the reduce
+    promises' datums. form "dag" is one launch, "phases" a reduce kernel and a
+    sweep kernel per iteration; both, and every block (16, 32, 64; 0 = the
+    largest that divides both sides), give the bits of the reference built
+    without fused multiply-add."""
+    if form not in SRAD_FORMS:
+        raise ValueError(f"srad: form {form!r} is not one of {sorted(SRAD_FORMS)}")
+    import numpy as np
+
+    j0 = np.ascontiguousarray(j0, dtype=np.float32)
+    if j0.ndim != 2:
+        raise ValueError("srad: j0 must be a matrix")
+    r1, r2, c1, c2 = (int(x) for x in roi)
+    rows, cols = j0.shape
+    out = np.empty_like(j0)
+    q = np.zeros(max(int(niter), 0), dtype=np.float32)
+    r = SradResult()
+    _check(lib().hclib_hip_srad(j0.ctypes.data, rows, cols, r1, r2, c1, c2, float(np.float32(lam)), niter, block,
+                                SRAD_FORMS[form], out.ctypes.data, q.ctypes.data, C.byref(r)), "hclib_hip_srad")
+    st = {k: getattr(r, k) for k, _ in SradResult._fields_}
+    st["q0sqr"] = q
+    return out, st
+
+
+def srad_image(rows: int, cols: int):
+    """The reference's input image: random_matrix (srand(7), rand() / RAND_MAX)
+    followed by expf (hclib_hip_srad_image, host only). It changes the
+    process's rand() state, as the reference does."""
+    import numpy as np
+
+    if rows < 1 or cols < 1:
+        _check(lib().hclib_hip_srad_image(rows, cols, None), "hclib_hip_srad_image")
+    j0 = np.empty((rows, cols), dtype=np.float32)
+    _check(lib().hclib_hip_srad_image(rows, cols, j0.ctypes.data), "hclib_hip_srad_image")
+    return j0
+
+
+def srad_bounds(rows: int, cols: int, roi, niter: int = 2, block: int = 0) -> dict:
+    """What a srad() launch creates (hclib_hip_srad_bounds), exact and on the
+    host alone: tasks, awaits, the block as resolved, the longest waiter list,
+    the bytes of device memory and the bytes the tasks move. Raises as the
+    launch would."""
+    r1, r2, c1, c2 = (int(x) for x in roi)
+    out = (C.c_uint64 * 6)()
+    _check(lib().hclib_hip_srad_bounds(rows, cols, r1, r2, c1, c2, niter, block, out), "hclib_hip_srad_bounds")
+    return dict(zip(("tasks", "awaits", "block", "max_waiters", "arena_bytes", "bytes_moved"), out))
 
 
 # --------------------------------------------------------------- BOTS Health

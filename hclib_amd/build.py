@@ -29,7 +29,7 @@ ARCH = "gfx950"
 SOURCES = ["module.hip", "forasync.hip", "uts.hip", "fib.hip", "sw.hip", "dag.hip", "hclib_api.hip", "locality.hip",
            "calib.hip", "atomic.hip", "cholesky.hip", "sort.hip", "sparselu.hip", "nqueens.hip",
            "strassen.hip", "health.hip", "floorplan.hip", "alignment.hip",
-           "fft.hip", "jacobi.hip", "bfs.hip", "cfd.hip"]
+           "fft.hip", "jacobi.hip", "bfs.hip", "cfd.hip", "srad.hip"]
 CFLAGS = [
     f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
     "-Wall", "-Wno-unused-function", "-Wno-unused-variable", "-Wno-unused-result",

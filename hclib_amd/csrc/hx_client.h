@@ -40,9 +40,11 @@ struct OnePromiseKind {
 //  3. hclib_hip_dag_end closes the launch begin opened, so it runs whether or
 //     not the kernel was launched; the residency code is returned before its
 //     code ("0 of n tasks ran" would hide why).
+// `datum_out`, where given, receives every promise's datum (srad.hip: a
+// promise that carries a value).
 template <class Launch>
 int launch_dag_group(const VersionGraph &g, int wgs_per_cu, const void *kern, int threads, const char *who,
-                     hclib_hip_dag_stats_t *st, Launch launch) {
+                     hclib_hip_dag_stats_t *st, Launch launch, uint64_t *datum_out = nullptr) {
     hclib_hip_dag_launch_t L;
     int rc = hclib_hip_dag_begin(g.ntasks(), g.ntasks(), 4, g.payload.data(), g.off.data(), g.ids.data(), nullptr,
                                  nullptr, wgs_per_cu, 0, &L);
@@ -52,7 +54,7 @@ int launch_dag_group(const VersionGraph &g, int wgs_per_cu, const void *kern, in
     }
     rc = check_resident(kern, L.grid, threads, 0, who);
     if (rc == HCLIB_HIP_OK) launch(L.grid, *(const DagView *)L.view);
-    const int rc_end = hclib_hip_dag_end(who, nullptr, nullptr, st);
+    const int rc_end = hclib_hip_dag_end(who, datum_out, nullptr, st);
     return rc ? rc : rc_end;
 }
 

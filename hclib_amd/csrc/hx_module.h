@@ -36,6 +36,7 @@ enum ArenaId {
     kArenaFft,         // class counters, the two ping-pong buffers and the twiddle table
     kArenaJacobi,      // f and the two ping-pong grids
     kArenaCfd,         // the mesh, the two ping-pong states, old and the step factors
+    kArenaSrad,        // the two ping-pong grids and the phases form's scalars
     kArenaUtsTables,  // rule / threshold / bucket tables of the last tree (Module::uts_tables_cached)
     kArenaCount
 };

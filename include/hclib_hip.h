@@ -96,6 +96,14 @@
  *                                    euler3d_cpu_double.ref.cpp:470-482), as awaits
  *                                    between (stage, block) tasks read off the
  *                                    mesh, in one launch of the device promise DAG
+ *   hclib_hip_srad                   the host thread's sums over the region of
+ *                                    interest and the two hclib_forasync_future
+ *                                    sweeps of Rodinia srad with the
+ *                                    hclib_future_wait after each (rodinia/srad/
+ *                                    srad.cpp; srad.ref.cpp:131-207), as one reduce
+ *                                    task whose promise carries q0sqr and one task
+ *                                    per block and iteration that awaits it, in one
+ *                                    launch of the device promise DAG
  *   hclib_hip_atomic_*,            the per-thread copies and the gather of
  *   hclib_hip_forasync_reduce        inc/hclib_atomic.h:37-42, 81-186 and
  *                                    src/hclib_atomic.c:34-54, one slot per wave
@@ -1302,6 +1310,61 @@ int hclib_hip_cfd(int nel, const double *areas, const int *neighbours, const dou
                   double *variables /* nelr * 5 */, hclib_hip_cfd_result_t *result);
 int hclib_hip_cfd_read_input(const char *path, double *areas, int *neighbours, double *normals, int64_t counts[2]);
 int hclib_hip_cfd_bounds(int nel, const int *neighbours, int iterations, int block, uint64_t out[6]);
+
+/* Rodinia SRAD, speckle-reducing anisotropic diffusion (test/performance-
+ * regression/full-apps/rodinia/srad/srad.cpp; the arithmetic as srad.ref.cpp
+ * states it): `niter` iterations over a rows x cols float image as ONE launch
+ * of the device promise DAG, bit-identical to the reference built without fused
+ * multiply-add (its mixed float / double expressions kept operation by
+ * operation) wherever the reference's result holds no NaN (a NaN arises only
+ * from 0/0, a flat cell inside a zero-variance region; its bits differ between
+ * processors).
+ * j0: rows * cols floats, row-major, the image after the reference's
+ * `J = (float)exp(I)` (hclib_hip_srad_image makes the reference's own).
+ * r1..r2, c1..c2: the region of interest, rows and columns, both ends included.
+ * lambda: the update's weight. j: rows * cols floats, the image after the last
+ * iteration; niter == 0 launches nothing and copies j0. q0sqr: niter floats or
+ * NULL: each iteration's scalar of the serial section (srad.ref.cpp:131-141),
+ * read back from the reduce promises' datums.
+ * block: the side of a task's square block, 16, 32 or 64, dividing both sides;
+ * 0 = the largest of 64, 32, 16 that does. The result does not depend on it.
+ *   HCLIB_HIP_SRAD_DAG     per iteration one reduce task R(it) (one wave, the
+ *       sums in the reference's order; its promise's datum is q0sqr) and one
+ *       task T(it, b) per block, which awaits R(it) and T(it - 1, b') for b and
+ *       its eight in-grid neighbours (hclib_amd/csrc/hx_srad_plan.h has why this
+ *       orders the overwrites of the two ping-pong grids). R(it + 1) awaits only
+ *       the blocks of the region of interest.
+ *   HCLIB_HIP_SRAD_PHASES  the same two bodies as one reduce kernel and one
+ *       sweep kernel per iteration, stream-ordered: the form with joins, for
+ *       comparison.
+ * result: tasks, puts, releases from the DAG launch (phases: tasks = the
+ * reduce waves and sweep workgroups run, no puts); awaits, iterations and
+ * bytes_moved are the plan's; block and form as run; kernel_ms.
+ * EINVAL, before the device is touched: a NULL image, a side that is not a
+ * positive multiple of 16 (the reference's own check), a block outside
+ * {16, 32, 64} or one that does not divide both sides, a region of interest
+ * that is empty or out of range, niter < 0, an unknown form, niter (nb + 1) >=
+ * 2^26 tasks or 2^32 awaits.
+ * hclib_hip_srad_bounds: host only, with the same checks, exact: out[0] tasks,
+ * [1] awaits, [2] the block as resolved, [3] the longest waiter list of a
+ * promise, [4] the bytes of device memory, [5] bytes_moved.
+ * hclib_hip_srad_image: host only: the reference's input, random_matrix
+ * (srand(7), rand() / (float)RAND_MAX) followed by expf, for any rows, cols >=
+ * 1. It changes the process's rand() state, as the reference does, and its
+ * last bit is this host's libm's. */
+typedef struct {
+    uint64_t tasks, puts, releases;            /* from the DAG launch */
+    uint64_t awaits, iterations, bytes_moved;  /* the plan's */
+    int block, form;                           /* as run */
+    double kernel_ms;                          /* device events around the launch (phases: around all iterations) */
+} hclib_hip_srad_result_t;
+#define HCLIB_HIP_SRAD_DAG 0
+#define HCLIB_HIP_SRAD_PHASES 1
+int hclib_hip_srad(const float *j0, int rows, int cols, int r1, int r2, int c1, int c2, float lambda, int niter,
+                   int block, int form /* 0 dag, 1 phases */, float *j /* rows * cols */,
+                   float *q0sqr /* niter, may be NULL */, hclib_hip_srad_result_t *result);
+int hclib_hip_srad_image(int rows, int cols, float *j0);
+int hclib_hip_srad_bounds(int rows, int cols, int r1, int r2, int c1, int c2, int niter, int block, uint64_t out[6]);
 
 #ifdef __cplusplus
 }
